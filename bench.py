@@ -12,12 +12,16 @@ are reported beside it. With --gpus N each rank decodes its own 10^7-record shar
 disjoint and there is no data-path collective ("weak" scaling). `value` is the whole-job
 aggregate in M updates/s, over all ranks.
 
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K frames and prints the
+headline alone. --dump-outputs DIR then also writes the columns the last timed frame produced
+(dump_outputs below). Everything else described here runs only with --full.
+
 The inputs come from the product encoder (config 4). Outside the timed regions every leg is
 checked once against the CPU oracle (oracle/nx_oracle.c, as the checker): decoded columns vs the
 oracle's decode of the same wire bytes (every row and column), encoded bytes vs the oracle's
 encode of the same columns. The oracle is also the cpu_baseline leg.
 
-Also reported on the same JSON line:
+Also reported on the same JSON line (--full):
   roofline       the decode's algorithmic bytes (W + 16 N) / mean time of one decode (HIP
                  events on the codec stream around the backlog) vs the 8 TB/s HBM3E peak;
   cpu_baseline   the C restatement of the reference decoder (oracle/, 1 core) on this host;
@@ -118,8 +122,11 @@ def warm(fn, sync, seconds=WARM_S):
         sync()
 
 
-def time_decode(codec, wire, out, n, steps, warmup, world, stream, flags=0, stream_of_frames=False):
+def time_decode(codec, wire, out, n, steps, warmup, world, stream, flags=0, stream_of_frames=False,
+                kernel_pass=True, after_wall=None):
     """Returns (wall seconds max over ranks, mean ms per frame from HIP events, last status).
+    kernel_pass=False: the wall-clock pass alone (its own events give the ms per frame);
+    after_wall(last status) is called right after the wall-clock pass, before any other decode.
     `wire` / `out` may be lists: frame j is wire[j % len] decoded into out[j % len] (distinct
     frames and column sets: with 3 of them at 10^7 records the working set, 924 MB, is past three
     times the 256 MiB Infinity Cache, so every decode streams from HBM). stream_of_frames: the
@@ -165,11 +172,13 @@ def time_decode(codec, wire, out, n, steps, warmup, world, stream, flags=0, stre
     torch.cuda.synchronize()
     barrier(world)
     wall = max_over_ranks(time.perf_counter() - t0, world)
+    if after_wall is not None:
+        after_wall(st)
     # The kernels' own time: the same frames again, the codec stream held by a short spin kernel
     # while the host enqueues them, so that the events do not count the GPU waiting for the
     # host's first submission (with the driver's --steps 20, ~50 us over 20 frames of 53 us)
     ms = e0.elapsed_time(e1) / steps
-    if GATE_CYCLES:
+    if GATE_CYCLES and kernel_pass:
         with torch.cuda.stream(stream):
             torch.cuda._sleep(GATE_CYCLES)
         e0.record(stream)
@@ -179,6 +188,41 @@ def time_decode(codec, wire, out, n, steps, warmup, world, stream, flags=0, stre
         torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / steps
     return wall, ms, st
+
+
+# --dump-outputs: at most this many rows of the last timed step's columns are written (4 float64
+# arrays of DUMP_ROWS rows: 48 MB, under the 64 MB a dump may take)
+DUMP_ROWS = 1_500_000
+DUMP_SEED = 0x5EED0D01
+
+
+def dump_outputs(dirname, out, n_rows, rank):
+    """--dump-outputs: what the last timed step left in its column set, as a caller of
+    nxg_decode_frames_async receives it (id and value of rows [0, n_rows)), written as float64
+    arrays DIR/<name>.npy. Above DUMP_ROWS rows a fixed sample is written: the same sorted row
+    numbers every run (seeded by DUMP_SEED and the row count alone). Every array is exact and
+    finite, so two builds compare with plain equality: ids are below 2^53, and a value (f64 bit
+    pattern, NaNs and infinities among them) is written as the two 32-bit halves of its bits.
+      rows.npy        the row numbers written
+      id.npy          Id of those rows
+      value_hi32.npy  bits 63..32 of the f64 value of those rows
+      value_lo32.npy  bits 31..0
+    Ranks above 0 write <name>_rank<r>.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    if n_rows > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, DUMP_ROWS, replace=False))
+    else:
+        rows = np.arange(n_rows)
+    idx = torch.from_numpy(rows.astype(np.int64)).to(out.id.device)
+    ids = out.id[:n_rows][idx].cpu().numpy().view(np.uint64)
+    bits = out.fixed[:n_rows][idx].cpu().numpy().view(np.uint64)
+    assert int(ids.max(initial=0)) < 2**53, "an Id does not fit a float64"
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for name, a in (("rows", rows), ("id", ids), ("value_hi32", bits >> np.uint64(32)),
+                    ("value_lo32", bits & np.uint64(0xFFFFFFFF))):
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a.astype(np.float64))
 
 
 def f64_kernel_name(codec):
@@ -1407,8 +1451,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--records", type=int, default=10_000_000)
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extras")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: the kernel-time pass and roofline, per-call, "
+                         "same-frame and length-run decodes, the oracle checks, the CPU baselines "
+                         "and the extras (a plain run times the headline steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's decoded columns (a fixed "
+                         "sample above 1.5 M rows) as DIR/<name>.npy")
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     import torch
     import netidx_amd
@@ -1426,32 +1478,41 @@ def main():
     # (working set 3 x (W + 16 N) = 924 MB at 10^7 records, past 3 x the 256 MiB Infinity Cache)
     wires = [wire, wire.clone(), wire.clone()]
     outs = [Columns(n, 0, 0, netidx_amd.LAYOUT_F64, "cuda") for _ in range(3)]
+
+    def after_wall(st):
+        # the last timed step decoded frame (steps - 1) % 3 into that column set
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outs[(args.steps - 1) % 3], int(st.n_rows), rank)
+
     wall, kms, st = time_decode(codec, wires, outs, n, args.steps, args.warmup, world, stream,
-                                stream_of_frames=True)
+                                stream_of_frames=True, kernel_pass=args.full,
+                                after_wall=after_wall)
     assert st.err_kind == 0 and st.path == 1 and st.n_rows == n, st
     kname = f64_kernel_name(codec)
-    # the same frame into the same columns every time (cache-assisted; earlier rounds' method)
-    _, kms_same, st1 = time_decode(codec, wire, outs[0], n, max(20, args.steps // 4), 2, world,
-                                   stream, stream_of_frames=True)
-    assert st1.err_kind == 0 and st1.path == 1 and st1.n_rows == n, st1
-    # one nxg_decode_updates_async per frame (no backlog), the same frames in rotation
-    _, kms_call, st3 = time_decode(codec, wires, outs, n, max(20, args.steps // 4), 2, world,
-                                   stream, stream_of_frames=False)
-    assert st3.err_kind == 0 and st3.path == 1 and st3.n_rows == n, st3
-    # the length-run decoder (any f64 frame; probe of frame j + 1 fused into the emit of frame j)
-    crun = codec_run_path(local)
-    crun.set_stream(stream.cuda_stream)
-    _, kms_run, st2 = time_decode(crun, wires, outs, n, max(20, args.steps // 4), 2, world,
-                                  stream, stream_of_frames=True)
-    assert st2.err_kind == 0 and st2.path == 1 and st2.n_rows == n, st2
-    crun.close()
-    # checker, outside the timed regions: every row of every column set against the oracle's
-    # decode of the same bytes
-    checked = sum(oracle_check_decode(wire, o, n) for o in outs) if rank == 0 else 0
+    if args.full:
+        # the same frame into the same columns every time (cache-assisted; earlier rounds' method)
+        _, kms_same, st1 = time_decode(codec, wire, outs[0], n, max(20, args.steps // 4), 2, world,
+                                       stream, stream_of_frames=True)
+        assert st1.err_kind == 0 and st1.path == 1 and st1.n_rows == n, st1
+        # one nxg_decode_updates_async per frame (no backlog), the same frames in rotation
+        _, kms_call, st3 = time_decode(codec, wires, outs, n, max(20, args.steps // 4), 2, world,
+                                       stream, stream_of_frames=False)
+        assert st3.err_kind == 0 and st3.path == 1 and st3.n_rows == n, st3
+        # the length-run decoder (any f64 frame; probe of frame j + 1 fused into the emit of
+        # frame j)
+        crun = codec_run_path(local)
+        crun.set_stream(stream.cuda_stream)
+        _, kms_run, st2 = time_decode(crun, wires, outs, n, max(20, args.steps // 4), 2, world,
+                                      stream, stream_of_frames=True)
+        assert st2.err_kind == 0 and st2.path == 1 and st2.n_rows == n, st2
+        crun.close()
+        # checker, outside the timed regions: every row of every column set against the oracle's
+        # decode of the same bytes
+        checked = sum(oracle_check_decode(wire, o, n) for o in outs) if rank == 0 else 0
 
     value = world * n * args.steps / wall / 1e6
     alg_bytes = nbytes + 16 * n
-    achieved = alg_bytes / (kms / 1e3) / 1e9
+    achieved = alg_bytes / (kms / 1e3) / 1e9  # in a plain run: the wall-clock pass's own events
 
     def frac(ms):
         return round(alg_bytes / (ms / 1e3) / 1e9 / HBM_PEAK_GBS, 4)
@@ -1475,8 +1536,13 @@ def main():
                    "records_per_gpu": n, "wire_bytes_per_gpu": nbytes,
                    "parallelism": f"shard-per-gpu x{world} (no data-path collective)"},
         "per_gpu_M_updates_s": round(value / world, 2),
-        "oracle_rows_checked": checked,
         "gib_per_s": round(world * alg_bytes * args.steps / wall / 2**30, 2),
+        "full": args.full,
+        "outputs_dumped_to": args.dump_outputs,
+    }
+    # everything below the headline: --full only (the figures take runs of their own)
+    line.update({
+        "oracle_rows_checked": checked,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                      "traffic": read_traffic(n, kname),
@@ -1502,8 +1568,8 @@ def main():
                                "kernels": " / ".join(KERNELS_DEC_F64),
                                "timed": "NXG_F64_PATH=run: the decoder of any f64 frame, the 3 "
                                         "frames in rotation as one backlog"},
-    }
-    if rank == 0 and world == 1:
+    } if args.full else {})
+    if args.full and rank == 0 and world == 1:
         host = wire.cpu().numpy()
         ups, reps, secs = cpu_baseline(host, n, args.cpu_seconds)
         model, nproc = host_cpu()
@@ -1521,7 +1587,7 @@ def main():
                 "kind": "port", "why_this_many": CPU_THREADS_WHY, "host_nproc": nproc,
                 "sample": f"full {n}-record frame cut at record boundaries into {T} sub-frames, "
                           f"decoded {reps}x ({secs:.1f} s) by oracle/nx_oracle.c on {T} threads"}
-    elif world > 1 and not args.no_extras:
+    elif args.full and world > 1 and not args.no_extras:
         try:
             ex = extras_multi_gpu(codec, world, rank, stream)
         except Exception as e:  # report, never lose the line (each leg catches its own below)

@@ -19,10 +19,10 @@ for rep in ${REPS:-1 2}; do
     for N in 10000000 100000000; do
       lib=$R/netidx_amd/build_ab/$name/libnxg_codec.so
       [ "$name" = base ] && lib=$R/netidx_amd/lib/libnxg_codec.so
-      NXG_LIB=$lib timeout -k 10 200 python3 $R/bench.py --steps 40 --warmup 3 --no-extras --cpu-seconds 0.1 --records $N > $R/gpurun_out/ab_${name}_${N}_$rep.json 2>/dev/null || exit 1
+      NXG_LIB=$lib timeout -k 10 200 python3 $R/bench.py --full --steps 40 --warmup 3 --no-extras --cpu-seconds 0.1 --records $N > $R/run_out/ab_${name}_${N}_$rep.json 2>/dev/null || exit 1
       python3 -c "
 import json,sys
-d=json.loads(open('$R/gpurun_out/ab_${name}_${N}_$rep.json').read().strip().splitlines()[-1])
+d=json.loads(open('$R/run_out/ab_${name}_${N}_$rep.json').read().strip().splitlines()[-1])
 print('$name', $N, 'rep $rep', 'kernel_ms', d['roofline']['kernel_ms'], 'frac', d['roofline']['frac'], flush=True)"
     done
   done

@@ -3,12 +3,12 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
-mkdir -p gpurun_out
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
-rc=$?; tail -2 gpurun_out/smoke.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 1000 python -u -m pytest tests -q -m gpu --maxfail=20 --timeout 300 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
-rc=$?; tail -3 gpurun_out/pytest_gpu.log; grep -E "^FAILED|^ERROR" gpurun_out/pytest_gpu.log | head -30
+mkdir -p run_out
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > run_out/smoke.log 2>&1
+rc=$?; tail -2 run_out/smoke.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 1000 python -u -m pytest tests -q -m gpu --maxfail=20 --timeout 300 --timeout-method thread > run_out/pytest_gpu.log 2>&1
+rc=$?; tail -3 run_out/pytest_gpu.log; grep -E "^FAILED|^ERROR" run_out/pytest_gpu.log | head -30
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err
-rc2=$?; cat gpurun_out/bench.json; [ $rc2 -eq 0 ] || { tail -5 gpurun_out/bench.err; exit $rc2; }
+timeout -k 10 600 python bench.py --full > run_out/bench.json 2> run_out/bench.err
+rc2=$?; cat run_out/bench.json; [ $rc2 -eq 0 ] || { tail -5 run_out/bench.err; exit $rc2; }
 exit $rc

@@ -1,8 +1,8 @@
 #!/bin/bash
 # GPU parity tests + one default bench line (each step under its own time limit).
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 600 python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1
-rc=$?; tail -3 gpurun_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.json 2> gpurun_out/bench.err
-rc=$?; cat gpurun_out/bench.json; [ $rc -eq 0 ] || { tail -5 gpurun_out/bench.err; exit $rc; }
+mkdir -p run_out
+timeout -k 10 600 python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout-method thread > run_out/pytest_gpu.log 2>&1
+rc=$?; tail -3 run_out/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > run_out/bench.json 2> run_out/bench.err
+rc=$?; cat run_out/bench.json; [ $rc -eq 0 ] || { tail -5 run_out/bench.err; exit $rc; }

@@ -6,10 +6,10 @@ set -o pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+mkdir -p run_out
 T="python -u -m pytest -x -q -m gpu --timeout 120 --timeout-method thread"
-timeout -k 10 300 $T tests/test_gpu_partition.py > gpurun_out/r06e_part.log 2>&1
-rc=$?; tail -3 gpurun_out/r06e_part.log; [ $rc -eq 0 ] || exit $rc
+timeout -k 10 300 $T tests/test_gpu_partition.py > run_out/r06e_part.log 2>&1
+rc=$?; tail -3 run_out/r06e_part.log; [ $rc -eq 0 ] || exit $rc
 bash scripts/gpu_r06d.sh || exit 1
-timeout -k 10 600 python -u bench.py > gpurun_out/r06e_bench.json 2> gpurun_out/r06e_bench.err
-rc=$?; cut -c1-300 gpurun_out/r06e_bench.json; exit $rc
+timeout -k 10 600 python -u bench.py --full > run_out/r06e_bench.json 2> run_out/r06e_bench.err
+rc=$?; cut -c1-300 run_out/r06e_bench.json; exit $rc
