@@ -188,6 +188,58 @@ bool nxg_encode_frames(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, u
                        uint64_t cap, uint64_t* len_out, uint64_t* chunk_len_out,
                        uint64_t cap_chunks, uint64_t* n_chunks, NetidxError* err);
 
+/* ---- subscriber write batches: publisher::To (netidx-netproto/src/publisher.rs:50-70) ------
+ * The other direction of a connection. nxg_decode_writes replaces the publisher's
+ * con.receive_batch(batch) loop (netidx/src/publisher/server.rs:660); nxg_encode_writes replaces
+ * the subscriber's queue_send(&To::Write(..)) / queue_send(&To::Unsubscribe(..)) loop
+ * (netidx/src/subscriber/connection.rs:384-399). Every message is varint(L) variant fields:
+ *   0 Subscribe { path, resolver: SocketAddr, timestamp: u64, permissions: u32, token: Bytes }
+ *   1 Unsubscribe(Id)
+ *   2 Write(Id, bool, Value, #[pack(default)] WriteId)
+ * Rows are the Write messages in wire order: id/tag/fixed/aux and the children mean what they
+ * mean for an Update, and the two further fields of a Write go to the companion NxgWriteCols
+ * (NxgColumns keeps its layout). Subscribe and Unsubscribe messages are validated and kept as raw
+ * control spans (ctl_row/ctl_off/ctl_len) with ctl_variant = the To variant (0 or 1).
+ * Synchronous calls only: the async ring, the multi-GPU calls and the sessions do not take To
+ * frames. */
+#define NXG_PATH_WRITES 6 /* NxgStatus.path of a To-frame decode */
+enum NxgWriteFlags {
+    NXG_WRITE_REPLY = 1, /* Write's bool: the writer wants a WriteResult */
+    NXG_WRITE_NO_WID = 2 /* no WriteId on the wire (an old peer, or one cut short by the length
+                            prefix): the caller allots one, as WriteId::default() does; wid[i]
+                            is 0 */
+};
+typedef struct NxgWriteCols {
+    uint32_t mem; /* NxgMem */
+    uint32_t pad;
+    uint64_t cap_rows;
+    uint8_t* wflags; /* NxgWriteFlags per row */
+    uint64_t* wid;   /* WriteId per row */
+} NxgWriteCols;
+bool nxg_write_cols_alloc(NxgCtx* ctx, uint64_t cap_rows, uint32_t mem, NxgWriteCols* out,
+                          NetidxError* err);
+void nxg_write_cols_free(NxgCtx* ctx, NxgWriteCols* cols);
+/* `frame`: host or device memory (a frame from nxg_session_recv_frame goes straight in). `out`
+ * must have the MIXED layout; `out` and `wout` are both device memory or both pinned host memory,
+ * and wout->cap_rows >= out->cap_rows. Capacity bounds for W bytes: rows <= W/5 (`05 02 00 00 10`),
+ * children <= W, ctl <= W/3 (`03 01 07`). n_heartbeat is 0. A malformed frame returns true with
+ * st->err_kind / err_offset of the first failing message and all counts 0, as nxg_decode_updates;
+ * false on misuse, a HIP failure or an exceeded capacity (NXG_CAPACITY in the message). */
+bool nxg_decode_writes(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColumns* out,
+                       NxgWriteCols* wout, NxgStatus* st, NetidxError* err);
+/* Each row becomes varint(L) 02 varint(id) (wflags & NXG_WRITE_REPLY) Value varint(wid), with
+ * L = lw(1 + vl(id) + 1 + |Value| + vl(wid)); NXG_WRITE_NO_WID is ignored (the reference encoder
+ * always writes the WriteId). Control spans (pre-encoded Subscribe / Unsubscribe messages) are
+ * copied from `heap` before row ctl_row[k]. in/win/heap/out all device memory, or all host memory.
+ * out NULL: the length only. A message longer than MAX_BATCH fails with TooBig. A batch whose total exceeds MAX_BATCH
+ * (0x3FFFFFFF bytes) is refused before anything is written: size it with nxg_encoded_writes_len
+ * and split the rows; the frame cut of nxg_encode_frames is not extended to write batches. */
+bool nxg_encoded_writes_len(NxgCtx* ctx, const NxgColumns* in, const NxgWriteCols* win,
+                            const uint8_t* heap, uint64_t* len_out, NetidxError* err);
+bool nxg_encode_writes(NxgCtx* ctx, const NxgColumns* in, const NxgWriteCols* win,
+                       const uint8_t* heap, uint8_t* out, uint64_t cap, uint64_t* len_out,
+                       NetidxError* err);
+
 /* ---- multi-GPU: one frame decoded in byte ranges, one batch encoded in shards -------------
  * One process per GPU. A frame of W bytes is cut into contiguous byte ranges; each GPU decodes
  * the messages that START in its range, reading past the range end as needed (messages never

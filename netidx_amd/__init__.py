@@ -1,4 +1,5 @@
-"""netidx_amd: MI355X-native batch-update codec for netidx's publisher->subscriber stream.
+"""netidx_amd: MI355X-native batch-update codec for netidx's publisher->subscriber stream, and
+for the subscriber->publisher write stream (publisher::To).
 
 The hot path (decode/encode of length-wrapped From::Update(Id, Value) batches) and the
 subscriber's update dispatch run in hand-written gfx950 HIP kernels behind the C ABI in
@@ -11,7 +12,8 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     PUB_UPDATE_CLIENT, SubTable, columns_from_arrays, frame_header,
                     frame_parse_header, frame_split, lib, Comm, NxgRange, range_link, Session,
                     msg_subscribe, msg_subscribed, msg_heartbeat, msg_parse, msg_update,
-                    TAG_UNSUBSCRIBED, Resolver, ResolverClient, TagView, TAG_BINS)
+                    TAG_UNSUBSCRIBED, Resolver, ResolverClient, TagView, TAG_BINS, WriteCols,
+                    NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
            "frame_split", "frame_header", "frame_parse_header", "LAYOUT_F64", "LAYOUT_MIXED",
@@ -20,4 +22,5 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "PubTable", "FrameReader", "PUB_UPDATE", "PUB_UPDATE_CHANGED", "PUB_UPDATE_CLIENT",
            "Comm", "NxgRange", "range_link", "Session", "msg_subscribe", "msg_subscribed",
            "msg_heartbeat", "msg_parse", "msg_update", "TAG_UNSUBSCRIBED", "Resolver",
-           "ResolverClient", "TagView", "TAG_BINS"]
+           "ResolverClient", "TagView", "TAG_BINS", "WriteCols", "NxgWriteCols", "WRITE_REPLY",
+           "WRITE_NO_WID", "PATH_WRITES"]

@@ -8,6 +8,9 @@ The Python surface mirrors the two seams that the codec replaces in the referenc
   message, and the whole frame is rejected, as in connection.rs:228-231.
 * ``Codec.encode_batch(cols)`` replaces the ``handle_updates`` -> ``queue_send`` loop
   (netidx/src/publisher/server.rs:610-612, netidx/src/channel.rs:177-202).
+* ``Codec.decode_writes(frame)`` / ``Codec.encode_writes(cols, wcols)`` are the other direction,
+  publisher::To: the publisher's ``con.receive_batch`` (publisher/server.rs:660) and the
+  subscriber's ``queue_send(&To::Write(..))`` loop (subscriber/connection.rs:384-399).
 
 The product path is the HIP library. There is no CPU fallback: if the shared library or a GPU
 is missing, the calls raise.
@@ -29,6 +32,9 @@ ERR_NAMES = {1: "UnknownTag", 2: "TooBig", 3: "InvalidFormat", 4: "BufferShort",
 LAYOUT_F64, LAYOUT_MIXED = 1, 2
 MEM_DEVICE, MEM_HOST = 0, 1
 HINT_MIXED = 1
+# To frames (nxg_decode_writes): NxgWriteFlags and the status path
+WRITE_REPLY, WRITE_NO_WID = 1, 2
+PATH_WRITES = 6
 
 
 class PackError(Exception):
@@ -62,6 +68,11 @@ class NxgColumns(C.Structure):
         ("ctl_row", C.c_void_p), ("ctl_off", C.c_void_p), ("ctl_len", C.c_void_p),
         ("ctl_variant", C.c_void_p),
     ]
+
+
+class NxgWriteCols(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("pad", C.c_uint32), ("cap_rows", C.c_uint64),
+                ("wflags", C.c_void_p), ("wid", C.c_void_p)]
 
 
 class NxgRange(C.Structure):
@@ -165,6 +176,18 @@ SIGNATURES = {
     "nxg_encode_frames": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p, C.c_void_p,
                                      C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64,
                                      C.POINTER(C.c_uint64), C.POINTER(NetidxError)]),
+    "nxg_write_cols_alloc": (C.c_bool, [C.c_void_p, C.c_uint64, C.c_uint32,
+                                        C.POINTER(NxgWriteCols), C.POINTER(NetidxError)]),
+    "nxg_write_cols_free": (None, [C.c_void_p, C.POINTER(NxgWriteCols)]),
+    "nxg_decode_writes": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NxgColumns),
+                                     C.POINTER(NxgWriteCols), C.POINTER(NxgStatus),
+                                     C.POINTER(NetidxError)]),
+    "nxg_encoded_writes_len": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns),
+                                          C.POINTER(NxgWriteCols), C.c_void_p,
+                                          C.POINTER(C.c_uint64), C.POINTER(NetidxError)]),
+    "nxg_encode_writes": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.POINTER(NxgWriteCols),
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                     C.POINTER(NetidxError)]),
     "nxg_decode_range": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                     C.POINTER(NxgColumns), C.POINTER(NxgRange),
                                     C.POINTER(NetidxError)]),
@@ -385,6 +408,45 @@ class Columns:
         out["n_heartbeat"] = self.s.n_heartbeat
         out["layout"] = self.s.layout
         return out
+
+
+class WriteCols:
+    """The two further fields of To::Write rows (NxgWriteCols): wflags (WRITE_REPLY |
+    WRITE_NO_WID) and wid (the WriteId) per row. torch tensors on `device` (pinned host memory
+    for 'cpu'), beside a Columns of at most cap_rows rows."""
+
+    def __init__(self, cap_rows, device="cuda"):
+        import torch
+        self.device = torch.device(device)
+        n = max(cap_rows, 1)
+        self.wflags = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self.wid = torch.zeros(n, dtype=torch.int64, device=self.device)
+        if self.device.type == "cpu":
+            self.wflags, self.wid = self.wflags.pin_memory(), self.wid.pin_memory()
+        self.s = NxgWriteCols()
+        self.s.mem = MEM_DEVICE if self.device.type == "cuda" else MEM_HOST
+        self.s.cap_rows = n
+        self.s.wflags, self.s.wid = self.wflags.data_ptr(), self.wid.data_ptr()
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)  # (as Columns: the zero fill is done)
+
+    def numpy(self, n_rows):
+        """Host copy of the first n_rows rows: {"wflags": u8, "wid": u64}."""
+        return {"wflags": self.wflags[:n_rows].cpu().numpy(),
+                "wid": self.wid[:n_rows].cpu().numpy().view(np.uint64)}
+
+
+def _frame_ptr(frame):
+    """(pointer, keep-alive) of a frame given as bytes, ndarray, tensor or device pointer."""
+    if isinstance(frame, (bytes, bytearray, memoryview)):
+        keep = np.frombuffer(bytes(frame), np.uint8)
+        return keep.ctypes.data, keep
+    if isinstance(frame, np.ndarray):
+        keep = np.ascontiguousarray(frame)
+        return keep.ctypes.data, keep
+    if hasattr(frame, "data_ptr"):
+        return frame.data_ptr(), frame
+    return int(frame), None
 
 
 class Codec:
@@ -654,6 +716,52 @@ class Codec:
         out = torch.empty(max(n, 16), dtype=torch.uint8, device=cols.device)
         m = self.encode_into(cols, heap, out.data_ptr(), n)
         assert m == n
+        return out[:n]
+
+    # ---- publisher::To: subscriber write batches ---------------------------------------------
+    def decode_writes(self, frame, cols=None, wcols=None, check=True):
+        """Decode one To frame (Subscribe / Unsubscribe / Write; host bytes or a device tensor):
+        returns (Columns, WriteCols). Rows are the Writes, with wcols.wflags / wcols.wid; the
+        other messages are control spans. A malformed frame raises PackError(kind, offset) (check);
+        last_status() and self.writes_status describe the decode."""
+        n = len(frame) if not hasattr(frame, "numel") else frame.numel()
+        if cols is None:
+            cols = Columns(n // 5 + 1, n + 1, n // 3 + 1, LAYOUT_MIXED,
+                           "cuda" if wcols is None else wcols.device)
+        if wcols is None:
+            wcols = WriteCols(cols.caps["rows"], cols.device)
+        ptr, keep = _frame_ptr(frame)
+        st, err = NxgStatus(), NetidxError()
+        ok = lib().nxg_decode_writes(self.ctx, C.c_void_p(ptr), n, C.byref(cols.s),
+                                     C.byref(wcols.s), C.byref(st), C.byref(err))
+        _check(ok, err)
+        self.writes_status = st
+        if check and st.err_kind:
+            raise PackError(st.err_kind, st.err_offset)
+        return cols, wcols
+
+    def encoded_writes_len(self, cols, wcols, heap=None):
+        n, err = C.c_uint64(0), NetidxError()
+        _check(lib().nxg_encoded_writes_len(self.ctx, C.byref(cols.s), C.byref(wcols.s),
+                                            _heap_ptr(heap), C.byref(n), C.byref(err)), err)
+        return n.value
+
+    def encode_writes_into(self, cols, wcols, heap, out_ptr, cap):
+        n, err = C.c_uint64(0), NetidxError()
+        _check(lib().nxg_encode_writes(self.ctx, C.byref(cols.s), C.byref(wcols.s),
+                                       _heap_ptr(heap), C.c_void_p(out_ptr), cap, C.byref(n),
+                                       C.byref(err)), err)
+        return n.value
+
+    def encode_writes(self, cols, wcols, heap=None):
+        """Encode rows as To::Write messages (control spans: pre-encoded Subscribe / Unsubscribe
+        messages in `heap`) to one frame payload, a uint8 tensor on the columns' device."""
+        import torch
+        n = self.encoded_writes_len(cols, wcols, heap)
+        out = torch.empty(max(n, 16), dtype=torch.uint8, device=cols.device)
+        if n:
+            m = self.encode_writes_into(cols, wcols, heap, out.data_ptr(), n)
+            assert m == n
         return out[:n]
 
     def decode_range(self, dframe, frame_len, begin, end, cols):

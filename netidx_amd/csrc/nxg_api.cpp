@@ -111,6 +111,10 @@ struct NxgCtx {
     bool dcols_valid = false;
     uint8_t* dheap = nullptr;
     size_t dheap_cap = 0;
+    // device staging of a host-resident NxgWriteCols (nxg_decode_writes / nxg_encode_writes)
+    uint8_t* dwflags = nullptr;
+    uint64_t* dwid = nullptr;
+    size_t dw_cap = 0;
     // in-flight async operations (completed in order by nxg_ctx_sync)
     struct Pending {
         int kind;  // 1 decode, 2 encode
@@ -207,8 +211,11 @@ bool is_device_ptr(const void* p) {
     return a.type == hipMemoryTypeDevice;
 }
 
-ColsDesc desc_of(const NxgColumns* c) {
+// w: the companion columns of a To frame's Write rows (null for From)
+ColsDesc desc_of(const NxgColumns* c, const NxgWriteCols* w = nullptr) {
     ColsDesc d{};
+    d.wflags = w ? w->wflags : nullptr;
+    d.wid = w ? w->wid : nullptr;
     d.cap_rows = c->cap_rows;
     d.cap_children = c->cap_children;
     d.cap_ctl = c->cap_ctl;
@@ -585,11 +592,12 @@ bool frame_to_device(NxgCtx* c, const uint8_t* frame, uint64_t len, const uint8_
 
 // *fast = 1 when the sequential-id f64 encoder was launched (finish_encode then reruns a batch it
 // declines on the tiled encoder); allow_seq = false forces the tiled encoder.
+// win: Write mode (To::Write rows; MIXED layout, device NxgWriteCols)
 bool enqueue_encode(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, uint8_t* out,
                     uint64_t cap, DevStatus* st, NetidxError* err, int* fast = nullptr,
-                    bool allow_seq = true) {
+                    bool allow_seq = true, const NxgWriteCols* win = nullptr) {
     if (fast) *fast = 0;
-    if (in->layout == NXG_LAYOUT_F64) {
+    if (in->layout == NXG_LAYOUT_F64 && !win) {
         const bool try_seq = allow_seq && !c->no_enc_seq && in->n_rows > 0;
         if (try_seq && c->enc_seq_left == 0) {
             HIPCHK(nxg_launch_enc_f64s(in->id, in->fixed, in->n_rows, out, cap, st, c->stream));
@@ -606,9 +614,9 @@ bool enqueue_encode(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, uint8_
     const uint64_t nt = nxg_enc_general_tiles(in->n_rows);
     if (!ensure_tstat(c, nt, err)) return false;
     if (!ensure_escratch(c, in->n_ctl ? in->n_ctl + 1 + in->n_rows : 1, err)) return false;
-    const ColsDesc d = desc_of(in);
+    const ColsDesc d = desc_of(in, win);
     HIPCHK(nxg_launch_enc_general(d, heap, out, cap, c->escratch, c->tstat, c->epoch, st,
-                                  c->grid_enc_gen, c->stream));
+                                  c->grid_enc_gen, c->stream, 0, win != nullptr));
     return true;
 }
 
@@ -838,6 +846,8 @@ void nxg_ctx_destroy(NxgCtx* c) {
     if (c->zlit) (void)hipFree(c->zlit);
     if (c->zrecs) (void)hipFree(c->zrecs);
     if (c->dheap) (void)hipFree(c->dheap);
+    if (c->dwflags) (void)hipFree(c->dwflags);
+    if (c->dwid) (void)hipFree(c->dwid);
     if (c->dst) (void)hipFree(c->dst);
     if (c->hst) (void)hipHostFree(c->hst);
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -1163,8 +1173,26 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
     return ok;
 }
 
+// Grows the device staging of a host-resident NxgWriteCols to `rows` rows.
+static bool ensure_dwcols(NxgCtx* c, uint64_t rows, NetidxError* err) {
+    if (c->dw_cap >= rows && c->dwflags) return true;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->dwflags) HIPCHK(hipFree(c->dwflags));
+    if (c->dwid) HIPCHK(hipFree(c->dwid));
+    c->dwflags = nullptr;
+    c->dwid = nullptr;
+    c->dw_cap = 0;
+    const size_t n = std::max<size_t>(rows, 1024);
+    HIPCHK(hipMalloc(&c->dwflags, n));
+    HIPCHK(hipMalloc(&c->dwid, n * 8));
+    c->dw_cap = n;
+    return true;
+}
+
+// win: the rows are To::Write messages (nxg_encode_writes), else From::Update
 static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, uint8_t* out,
-                        uint64_t cap, uint64_t* len_out, NetidxError* err) {
+                        uint64_t cap, uint64_t* len_out, NetidxError* err,
+                        const NxgWriteCols* win = nullptr) {
     if (!c || !in) {
         set_err(err, "null argument");
         return false;
@@ -1177,6 +1205,20 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
     const bool host = in->mem == NXG_MEM_HOST || !is_device_ptr(in->id);
     const NxgColumns* din = in;
     NxgColumns view;
+    NxgWriteCols wview{};
+    const NxgWriteCols* dwin = win;
+    if (win && host && in->n_rows) {
+        if (!ensure_dwcols(c, in->n_rows, err)) return false;
+        HIPCHK(hipMemcpyAsync(c->dwflags, win->wflags, in->n_rows, hipMemcpyHostToDevice,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(c->dwid, win->wid, in->n_rows * 8, hipMemcpyHostToDevice,
+                              c->stream));
+        wview = *win;
+        wview.mem = NXG_MEM_DEVICE;
+        wview.wflags = c->dwflags;
+        wview.wid = c->dwid;
+        dwin = &wview;
+    }
     const uint8_t* dheap = heap;
     uint8_t* dout = out;
     uint64_t heap_len = 0;
@@ -1216,20 +1258,29 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
     DevStatus* st;
     uint32_t slot;
     uint64_t total = 0;
-    // pass 1 (sizing) when writing to a host buffer; a device buffer is written directly
-    if (host && out) {
+    // pass 1 (sizing) when writing to a host buffer; a device buffer is written directly. A
+    // write batch is also sized first when its buffer could take more than MAX_BATCH bytes, so
+    // that such a batch is refused before anything is written (a smaller buffer bounds the
+    // writes itself, and the call fails below).
+    const bool size_first = win && out && cap > kMaxBatch;
+    if ((host && out) || size_first) {
         if (!begin_call(c, &st, &slot, err)) return false;
         int fast = 0;
-        const bool ok = enqueue_encode(c, din, dheap, nullptr, 0, st, err, &fast);
+        const bool ok = enqueue_encode(c, din, dheap, nullptr, 0, st, err, &fast, true, dwin);
         if (!end_call(c, err) || !ok) return false;
         if (!finish_encode(c, din, st, slot, &total, 0, false, err, false, fast, dheap, nullptr))
             return false;
+        if (win && total > kMaxBatch) {
+            set_err(err, "write batch of %llu bytes exceeds MAX_BATCH (%llu): split the rows",
+                    (unsigned long long)total, (unsigned long long)kMaxBatch);
+            return false;
+        }
         if (total > cap) {
             set_err(err, "output buffer too small: need %llu bytes, have %llu",
                     (unsigned long long)total, (unsigned long long)cap);
             return false;
         }
-        if (c->dframe_cap < total + 16) {
+        if (host && c->dframe_cap < total + 16) {
             HIPCHK(hipStreamSynchronize(c->stream));
             if (c->dframe) HIPCHK(hipFree(c->dframe));
             c->dframe = nullptr;
@@ -1237,16 +1288,21 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
             HIPCHK(hipMalloc(&c->dframe, n));
             c->dframe_cap = n;
         }
-        dout = c->dframe;
+        if (host) dout = c->dframe;
         cap = total;
     }
     if (!begin_call(c, &st, &slot, err)) return false;
     int fast = 0;
-    const bool ok = enqueue_encode(c, din, dheap, dout, out ? cap : 0, st, err, &fast);
+    const bool ok = enqueue_encode(c, din, dheap, dout, out ? cap : 0, st, err, &fast, true, dwin);
     if (!end_call(c, err) || !ok) return false;
     if (!finish_encode(c, din, st, slot, &total, cap, dout != nullptr, err, false, fast, dheap,
                        dout))
         return false;
+    if (win && total > kMaxBatch) {
+        set_err(err, "write batch of %llu bytes exceeds MAX_BATCH (%llu): split the rows",
+                (unsigned long long)total, (unsigned long long)kMaxBatch);
+        return false;
+    }
     if (host && out && total) {
         HIPCHK(hipMemcpyAsync(out, dout, total, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1841,6 +1897,194 @@ bool nxg_encode_updates(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
         return false;
     }
     return encode_impl(c, in, heap, out, cap, len_out, err);
+}
+
+// ---- subscriber write batches: publisher::To (publisher.rs:50-70) ------------------------------
+bool nxg_write_cols_alloc(NxgCtx* c, uint64_t cap_rows, uint32_t mem, NxgWriteCols* out,
+                          NetidxError* err) {
+    if (!c || !out) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (mem != NXG_MEM_DEVICE && mem != NXG_MEM_HOST) {
+        set_err(err, "unknown memory kind %u", mem);
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    memset(out, 0, sizeof *out);
+    out->mem = mem;
+    out->cap_rows = cap_rows;
+    const size_t n = std::max<uint64_t>(cap_rows, 2);
+    const hipError_t e1 = mem == NXG_MEM_DEVICE
+                              ? hipMalloc((void**)&out->wflags, n)
+                              : hipHostMalloc((void**)&out->wflags, n, hipHostMallocDefault);
+    const hipError_t e2 = e1 != hipSuccess ? e1
+                          : mem == NXG_MEM_DEVICE
+                              ? hipMalloc((void**)&out->wid, n * 8)
+                              : hipHostMalloc((void**)&out->wid, n * 8, hipHostMallocDefault);
+    if (e2 != hipSuccess) {
+        set_err(err, "write column allocation of %zu rows failed: %s", n, hipGetErrorString(e2));
+        nxg_write_cols_free(c, out);
+        return false;
+    }
+    return true;
+}
+
+void nxg_write_cols_free(NxgCtx* c, NxgWriteCols* w) {
+    if (!w) return;
+    if (c) (void)hipSetDevice(c->device);
+    void* ps[] = {w->wflags, w->wid};
+    for (void* p : ps) {
+        if (!p) continue;
+        if (w->mem == NXG_MEM_DEVICE) (void)hipFree(p);
+        else (void)hipHostFree(p);
+    }
+    memset(w, 0, sizeof *w);
+}
+
+// Replaces con.receive_batch(batch) on a publisher's connection (publisher/server.rs:660): the
+// general decoder's To instantiation (nxg_decode_gen.hip), synchronously.
+bool nxg_decode_writes(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgColumns* out,
+                       NxgWriteCols* wout, NxgStatus* ust, NetidxError* err) {
+    if (!c || !out || !wout || !ust || (!frame && len)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    // (the argument checks come before any use of the context)
+    if (!mixed_capable(out) || !out->id || !out->fixed) {
+        set_err(err, "write batches decode into MIXED-layout columns");
+        return false;
+    }
+    if (!wout->wflags || !wout->wid || wout->cap_rows < out->cap_rows) {
+        set_err(err, "write columns hold %llu rows, the columns %llu",
+                (unsigned long long)wout->cap_rows, (unsigned long long)out->cap_rows);
+        return false;
+    }
+    if (out->mem != wout->mem || (out->mem != NXG_MEM_DEVICE && out->mem != NXG_MEM_HOST)) {
+        set_err(err, "columns and write columns must both be device or both pinned host memory");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (len >= (1ull << 40)) {
+        set_err(err, "frame too large (%llu bytes)", (unsigned long long)len);
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    const bool host_out = out->mem == NXG_MEM_HOST;
+    NxgColumns* target = out;
+    NxgColumns view;
+    NxgWriteCols wtarget = *wout;
+    if (host_out) {
+        if (!ensure_dcols(c, out, err) || !ensure_dwcols(c, out->cap_rows, err)) return false;
+        view = staged_view(c, out);
+        target = &view;
+        wtarget.wflags = c->dwflags;
+        wtarget.wid = c->dwid;
+    } else {
+        // every array a kernel writes through must be device memory
+        const void* ps[] = {out->id,     out->tag,     out->fixed,   out->aux,
+                            out->ctag,   out->cfixed,  out->caux,    out->ctl_row,
+                            out->ctl_off, out->ctl_len, out->ctl_variant, wout->wflags, wout->wid};
+        for (const void* p : ps) {
+            if (!is_device_ptr(p)) {
+                set_err(err, "a column array is not device memory");
+                return false;
+            }
+        }
+    }
+    const uint8_t* df;
+    if (!frame_to_device(c, frame, len, &df, err)) return false;
+    DevStatus* st;
+    uint32_t slot;
+    if (!begin_call(c, &st, &slot, err)) return false;
+    bool ok = ensure_glws(c, nxg_dec_gen_scratch_bytes(len), err);
+    if (ok) {
+        const ColsDesc d = desc_of(target, &wtarget);
+        const hipError_t le =
+            nxg_launch_dec_gen(df, len, d, c->glws, c->gruns,
+                               c->gruns + (size_t)gdec2::MAX_RUNS * gdec2::RUN_WORDS,
+                               c->wgs_dec_gen, st, c->stream, true);
+        if (le != hipSuccess) {
+            set_err(err, "To decode launch failed: %s", hipGetErrorString(le));
+            ok = false;
+        }
+    }
+    if (!end_call(c, err) || !ok) return false;
+    NxgStatus s;
+    if (!finish_decode(c, df, len, target, FAST_NONE, st, slot, &s, err)) return false;
+    s.path = NXG_PATH_WRITES;
+    s.n_heartbeat = 0;
+    out->layout = NXG_LAYOUT_MIXED;
+    out->n_heartbeat = 0;
+    if (s.err_kind == NXG_CAPACITY || (!s.err_kind && (s.n_rows > out->cap_rows ||
+                                                       s.n_children > out->cap_children ||
+                                                       s.n_ctl > out->cap_ctl))) {
+        out->n_rows = out->n_children = out->n_ctl = 0;
+        set_err(err, "column capacity exceeded (NXG_CAPACITY): the frame holds %llu rows, %llu "
+                     "children, %llu control messages",
+                (unsigned long long)s.n_rows, (unsigned long long)s.n_children,
+                (unsigned long long)s.n_ctl);
+        return false;
+    }
+    if (s.err_kind) s.n_rows = s.n_children = s.n_ctl = 0;  // the frame fails as a whole
+    if (host_out && !s.err_kind) {
+        target->n_rows = s.n_rows;
+        target->n_children = s.n_children;
+        target->n_ctl = s.n_ctl;
+        if (s.n_rows) {
+            HIPCHK(hipMemcpyAsync(wout->wflags, c->dwflags, s.n_rows, hipMemcpyDeviceToHost,
+                                  c->stream));
+            HIPCHK(hipMemcpyAsync(wout->wid, c->dwid, s.n_rows * 8, hipMemcpyDeviceToHost,
+                                  c->stream));
+        }
+        NxgColumns hv = *out;
+        if (!copy_cols_d2h(c, target, &hv, err)) return false;
+    }
+    out->n_rows = s.n_rows;
+    out->n_children = s.n_children;
+    out->n_ctl = s.n_ctl;
+    *ust = s;
+    return true;
+}
+
+static bool writes_args_ok(NxgCtx* c, const NxgColumns* in, const NxgWriteCols* win,
+                           NetidxError* err) {
+    if (!c || !in || !win) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (in->layout != NXG_LAYOUT_MIXED || !mixed_capable(in)) {
+        set_err(err, "write batches encode from MIXED-layout columns");
+        return false;
+    }
+    if (in->n_rows && (!win->wflags || !win->wid || win->cap_rows < in->n_rows)) {
+        set_err(err, "write columns hold %llu rows, the batch %llu",
+                (unsigned long long)win->cap_rows, (unsigned long long)in->n_rows);
+        return false;
+    }
+    if (in->n_rows && (in->mem != win->mem || is_device_ptr(in->id) != is_device_ptr(win->wid))) {
+        set_err(err, "columns and write columns must both be device or both host memory");
+        return false;
+    }
+    return true;
+}
+
+bool nxg_encoded_writes_len(NxgCtx* c, const NxgColumns* in, const NxgWriteCols* win,
+                            const uint8_t* heap, uint64_t* len_out, NetidxError* err) {
+    if (!writes_args_ok(c, in, win, err)) return false;
+    return encode_impl(c, in, heap, nullptr, 0, len_out, err, win);
+}
+
+// Replaces the subscriber's queue_send(&To::Write(..)) loop (subscriber/connection.rs:384-399):
+// the general encoder's rows kernel in Write mode (nxg_encode_general.hip).
+bool nxg_encode_writes(NxgCtx* c, const NxgColumns* in, const NxgWriteCols* win,
+                       const uint8_t* heap, uint8_t* out, uint64_t cap, uint64_t* len_out,
+                       NetidxError* err) {
+    if (!writes_args_ok(c, in, win, err)) return false;
+    return encode_impl(c, in, heap, out, cap, len_out, err, win);
 }
 
 bool nxg_encode_updates_async(NxgCtx* c, const NxgColumns* din, const uint8_t* dheap,

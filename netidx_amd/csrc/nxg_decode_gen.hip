@@ -2,6 +2,14 @@
 // tag, nesting, errors. Replaces the receive_batch_fn loop (netidx/src/channel.rs:504-521) for
 // frames the homogeneous-f64 kernels do not take.
 //
+// The same passes decode a publisher's incoming To stream (Subscribe / Unsubscribe / Write,
+// netidx-netproto/src/publisher.rs:50-70; con.receive_batch in publisher/server.rs:660): the
+// message grammar is a compile-time parameter G (FromG / ToG, nxg_msg.h) of every function below,
+// and each kernel is instantiated once per grammar (nxg_gen_*_kernel<FromG>, <ToG>). The chain
+// following is the same for both; G sets what a guessed start looks like (the row variant byte,
+// a Write's bool before and WriteId after its value), what counts as a row, and what the
+// bucketed emit reads around the value.
+//
 // Message boundaries form a pointer chain (len_wrapped_decode, pack.rs:537-555): a message's
 // length prefix says where the next one starts. The chain is followed in parallel, with the
 // same run structure as the f64 decoder (nxg_decode_f64.hip):
@@ -70,6 +78,7 @@ struct LaneRes {
 
 // Structural walk of the messages that start in [e, end) (skim_msg: lengths, variants, child
 // slots). Only a broken length prefix is an error here; content errors are the emit pass's.
+template <class G>
 NXG_DEV void walk(const Src& s, uint64_t e, uint64_t end, LaneRes& r, uint32_t budget) {
     r.x = e;
     r.rows = r.ctl = r.hb = 0;
@@ -83,7 +92,7 @@ NXG_DEV void walk(const Src& s, uint64_t e, uint64_t end, LaneRes& r, uint32_t b
     while (pos < stop) {
         MsgInfo mi;
         uint64_t ch = 0;
-        const uint32_t err = skim_msg(s, pos, mi, ch, work, budget);
+        const uint32_t err = skim_msg<G>(s, pos, mi, ch, work, budget);
         if (err == E_BUDGET) {
             r.st = S_EXH;
             return;
@@ -94,9 +103,9 @@ NXG_DEV void walk(const Src& s, uint64_t e, uint64_t end, LaneRes& r, uint32_t b
             r.x = pos;
             return;
         }
-        if (mi.variant == 4) r.rows++;
+        if (mi.variant == G::kRow) r.rows++;
         else r.ctl++;
-        r.hb += mi.variant == 5;
+        if constexpr (!G::kTo) r.hb += mi.variant == 5;
         r.children += ch;
         pos = mi.next;
     }
@@ -108,18 +117,40 @@ NXG_DEV void walk(const Src& s, uint64_t e, uint64_t end, LaneRes& r, uint32_t b
 // fit in the message, that a fixed-size value fills it exactly, and that the next position
 // looks like a message start (length >= 2, variant <= 6) or is the frame end. Only the
 // candidate's own bytes are guaranteed to be in the LDS image.
+// A Write (ToG) has its bool (0 or 1) between the id and the value, and the value does not end
+// the message: the WriteId follows, 0 (an old peer) to 10 bytes that form exactly one varint.
+NXG_DEV bool wid_fits(const Src& s, uint64_t a, uint64_t next) {
+    const uint64_t n = next - a;  // (a > next: a large n)
+    if (n > 10) return false;
+    if (n == 0) return true;
+    // its last two bytes decide (a guess: the bytes before them are not looked at)
+    if (s.any_byte(next - 1) & 0x80u) return false;
+    return n == 1 || (s.any_byte(next - 2) & 0x80u) != 0u;
+}
+// does the value (or its last part) that ends at `end` end the message as the grammar requires?
+template <class G>
+NXG_DEV bool ends_msg(const Src& s, uint64_t end, uint64_t next) {
+    if constexpr (G::kTo) return wid_fits(s, end, next);
+    return end == next;
+}
+template <class G>
 NXG_DEV bool plausible(const Src& s, uint64_t p, uint32_t nb, uint64_t L) {
     const uint64_t next = p + L;  // total size = nb + L - vl(L) = L for a minimal prefix
     if (next > s.W) return false;
     uint64_t q = p + nb + 1;  // id varint
     uint32_t k = 0;
     while (k < 10 && q + k < next && (s.img_byte(q + k) & 0x80u)) k++;
-    const uint64_t tp = q + k + 1;  // value tag
+    uint64_t tp0 = q + k + 1;  // value tag
+    if constexpr (G::kTo) {    // ... after the bool
+        if (k == 10 || tp0 >= next || s.img_byte(tp0) > 1u) return false;
+        tp0++;
+    }
+    const uint64_t tp = tp0;
     if (k == 10 || tp >= next) return false;
     const uint32_t t = s.img_byte(tp);
     if (t >= 28u) return false;
     const uint32_t f1 = fixed_size1(t);
-    if (f1 && tp + f1 != next) return false;
+    if (f1 && !ends_msg<G>(s, tp + f1, next)) return false;
     const bool vint = t == 1 || t == 3 || t == 5 || t == 7;
     const bool text = t == 12 || t == 13 || t == 18;
     if (vint || text) {  // the varint payload, or text length + text, fills the message exactly
@@ -131,7 +162,7 @@ NXG_DEV bool plausible(const Src& s, uint64_t p, uint32_t nb, uint64_t L) {
             v |= (uint64_t)(b & 0x7fu) << (7 * i);
             i++;
         } while (b & 0x80u);
-        if ((vint ? a + i : a + i + v) != next) return false;
+        if (!ends_msg<G>(s, vint ? a + i : a + i + v, next)) return false;
     }
     if (t == 19) {  // Array: an empty one ends the message, elements fit, the first tag is valid
         uint64_t v = 0, a = tp + 1;
@@ -142,7 +173,8 @@ NXG_DEV bool plausible(const Src& s, uint64_t p, uint32_t nb, uint64_t L) {
             v |= (uint64_t)(b & 0x7fu) << (7 * i);
             i++;
         } while (b & 0x80u);
-        if (v == 0 ? a + i != next : (a + i + v > next || s.any_byte(a + i) >= 28u)) return false;
+        if (v == 0 ? !ends_msg<G>(s, a + i, next) : (a + i + v > next || s.any_byte(a + i) >= 28u))
+            return false;
     }
     if (next == s.W) return true;
     if (next + 2 > s.W) return false;  // no room for a message (>= 2 bytes)
@@ -157,13 +189,15 @@ NXG_DEV bool plausible(const Src& s, uint64_t p, uint32_t nb, uint64_t L) {
         if (b1 == 0u || b1 >= 0x80u) return false;
         v = s.any_byte(next + 2);
     }
-    return v <= 6u;
+    return v <= G::kMaxVariant;
 }
 
 // First position in [c, stop) that starts a plausible Update (see plausible). Candidates come
 // from a SWAR scan for the Update variant byte (4) one or two bytes after a 1- or 2-byte length
 // varint. Only Updates are guessed: a Heartbeat or Unsubscribed accepts almost any bytes; a
 // chunk that starts with one, or a wrong guess, is resolved exactly by the repair.
+// (ToG: the same for Writes, variant byte 2.)
+template <class G>
 NXG_DEV uint64_t speculate(const Src& s, uint64_t c, uint64_t stop, uint32_t& tries) {
     if (c >= stop) return NONE;
     const uint64_t rc = c - s.t0;  // 64-aligned, inside the image with 68 bytes to spare
@@ -172,10 +206,10 @@ NXG_DEV uint64_t speculate(const Src& s, uint64_t c, uint64_t stop, uint32_t& tr
 #pragma unroll
     for (int k = 0; k < 16; k++) {
         const uint32_t x = alignbyte(w[k + 1], w[k], 1);  // bytes c+4k+1 .. c+4k+4
-        e4 |= (uint64_t)nib(zero_bytes(x ^ 0x04040404u)) << (4 * k);
+        e4 |= (uint64_t)nib(zero_bytes(x ^ (0x01010101u * G::kRow))) << (4 * k);
     }
     const uint32_t x16 = alignbyte(w[17], w[16], 1);  // byte c+65 (for 2-byte-length starts)
-    bool e4_64 = (x16 & 0xffu) == 4u;
+    bool e4_64 = (x16 & 0xffu) == G::kRow;
 #pragma unroll 1
     while (e4 || e4_64) {
         uint32_t q;  // variant byte at c+1+q
@@ -201,11 +235,11 @@ NXG_DEV uint64_t speculate(const Src& s, uint64_t c, uint64_t stop, uint32_t& tr
                 if (b0 < 0x80u || b1 == 0u || b1 >= 0x80u) continue;
                 L = (b0 & 0x7fu) | (b1 << 7);
             } else {
-                if (b0 < 4u || b0 >= 0x80u) continue;
+                if (b0 < G::kMinRow || b0 >= 0x80u) continue;
                 L = b0;
             }
             tries++;
-            if (plausible(s, p, form == 0 ? 2u : 1u, L)) return p;
+            if (plausible<G>(s, p, form == 0 ? 2u : 1u, L)) return p;
         }
     }
     return NONE;
@@ -223,6 +257,7 @@ struct TileOut {
 // Resolve one tile (its bytes are in the wave's LDS image `s`). `entry` is the exact first
 // message start at/after the tile start, or NONE (guess it). Sets this lane's word (lwo)
 // and returns the tile's totals. Wave-level: no block barriers.
+template <class G>
 NXG_DEV TileOut process_tile(const Src& s, uint64_t t0, uint64_t entry, uint32_t& lwo,
                              uint32_t& tries) {
     const uint32_t lane = __lane_id();
@@ -240,7 +275,7 @@ NXG_DEV TileOut process_tile(const Src& s, uint64_t t0, uint64_t entry, uint32_t
         has = entry < stop;  // the anchor lane (lanes before it: no start)
         e = has ? entry : NONE;
     } else {
-        e = speculate(s, c, stop, tries);
+        e = speculate<G>(s, c, stop, tries);
         has = e != NONE;
     }
     // anchor = the lane holding the entry, else the first lane with a guess
@@ -275,7 +310,7 @@ NXG_DEV TileOut process_tile(const Src& s, uint64_t t0, uint64_t entry, uint32_t
     uint32_t budget = (lane == a && entry != NONE) ? kExact.budget : kBounded.budget;
 #pragma unroll 1
     for (;;) {
-        if (need) walk(s, e, cend, r, budget);
+        if (need) walk<G>(s, e, cend, r, budget);
         need = false;
         if (++rounds > 2 * 64 + 4) {
             errlane = -2;  // logic error guard: reported as a timeout, never a hang
@@ -391,6 +426,7 @@ struct RunSum {
     uint32_t rounds, tries;
     uint64_t why;
 };
+template <class G>
 NXG_DEV RunSum run_tiles(const uint8_t* __restrict__ wire, uint64_t W, uint64_t b, uint64_t e,
                          uint64_t entry, uint32_t* __restrict__ lws, uint8_t* buf,
                          uint64_t old_last, bool& merged, int64_t* d) {
@@ -414,7 +450,7 @@ NXG_DEV RunSum run_tiles(const uint8_t* __restrict__ wire, uint64_t W, uint64_t 
         uint32_t lwv;
         const bool cmp_t = cmp && t <= old_last;
         const uint32_t ow = cmp_t ? lws[t * 64 + lane] : NOSTART;
-        const TileOut to = process_tile(s, t0, cur, lwv, tries);
+        const TileOut to = process_tile<G>(s, t0, cur, lwv, tries);
         lws[t * 64 + lane] = lwv;
         if (cmp_t && !to.ek) {
             const bool hn = lw_off(lwv) != NOSTART, ho = lw_off(ow) != NOSTART;
@@ -464,12 +500,13 @@ NXG_DEV RunSum run_tiles(const uint8_t* __restrict__ wire, uint64_t W, uint64_t 
     return rs;
 }
 
+// ---- pass 1: count ---------------------------------------------------------------------------
 }  // namespace
 
-// ---- pass 1: count ---------------------------------------------------------------------------
 #ifndef NXG_GEN_COUNT_OCC
 #define NXG_GEN_COUNT_OCC 3  // waves per SIMD (4: 128 VGPRs, and 128 B/lane of scratch)
 #endif
+template <class G>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(NXG_GEN_COUNT_OCC))) void nxg_gen_count_kernel(
     const uint8_t* __restrict__ wire, uint64_t W, uint64_t nt, uint32_t* __restrict__ lws,
     uint64_t* __restrict__ runs, DevStatus* __restrict__ st, DevStatus* zst, uint64_t* __restrict__ fix) {
@@ -482,7 +519,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(NXG_GEN_COU
     bool merged;
     int64_t d[3];
     const RunSum rs =
-        run_tiles(wire, W, b, e, b == 0 ? 0ull : NONE, lws, bufs[w], NONE, merged, d);
+        run_tiles<G>(wire, W, b, e, b == 0 ? 0ull : NONE, lws, bufs[w], NONE, merged, d);
     if (lane < R_WORDS) {
         const uint64_t v[R_WORDS] = {rs.spec, rs.exit, rs.rows, rs.ch, rs.ctl, rs.err, 0, 0};
         uint64_t x = v[0];
@@ -546,6 +583,7 @@ NXG_DEV uint64_t res_scan_max(uint64_t v, uint64_t* tmp) {
     return ex > m ? ex : m;
 }
 
+template <class G>
 __global__ __launch_bounds__(RES_TPB) void nxg_gen_resolve_kernel(
     const uint8_t* __restrict__ wire, uint64_t W, uint64_t nt, uint32_t R,
     uint32_t* __restrict__ lws, uint64_t* __restrict__ runs, uint64_t* __restrict__ base,
@@ -614,7 +652,7 @@ __global__ __launch_bounds__(RES_TPB) void nxg_gen_resolve_kernel(
             const uint64_t old_last = oerr ? (oerr & POSM) / TILE : e - 1;
             bool merged;
             int64_t d[3];
-            const RunSum rs = run_tiles(wire, W, b, e, XF, lws, buf, old_last, merged, d);
+            const RunSum rs = run_tiles<G>(wire, W, b, e, XF, lws, buf, old_last, merged, d);
             if (tid < R_WORDS) {
                 // merged: the old chain from the meeting point on stands (exit, error)
                 const uint64_t v[R_WORDS] = {
@@ -639,7 +677,7 @@ __global__ __launch_bounds__(RES_TPB) void nxg_gen_resolve_kernel(
         from = F;  // run F is now on the true chain; an error in it is found next round
     }
     if (tid == 0) {
-        st->path = 2;
+        st->path = G::kPath;
         st->diag[0] = fixes;
     }
     // prefix sums of the run totals -> bases
@@ -673,7 +711,6 @@ __global__ __launch_bounds__(RES_TPB) void nxg_gen_resolve_kernel(
         st->n_ctl = tk;
     }
 }
-
 // ---- pass 3: emit ----------------------------------------------------------------------------
 // Two kernels. The emit kernel is type-bucketed and message-parallel; per tile:
 //   1. each lane walks only the length chain of the messages that start in its chunk (from the
@@ -733,7 +770,9 @@ NXG_DEV uint64_t fix_value(const LdsSrc& s, uint32_t t, uint64_t p, int n) {
 // number of child slots (K_ARR) from bit 8. The Update bit is exact for every well-formed
 // message (it sets the row / control numbering); anything unusual, or a message not wholly in
 // the image, is K_OTHER.
+// (ToG: "Update" reads "Write"; its bool must be 0 or 1 here, its WriteId is emit_fast's.)
 constexpr uint32_t C_UPD = 16;
+template <class G>
 NXG_DEV uint32_t classify(const Src& s, uint64_t p) {
     const LdsSrc ls{s.lds, s.t0};
     uint64_t q = p, L;
@@ -742,13 +781,18 @@ NXG_DEV uint32_t classify(const Src& s, uint64_t p) {
     const uint64_t take = L - vl64(L);
     const uint64_t lim = take < s.W - q ? q + take : s.W;
     const uint32_t variant = s.any_byte(q++);
-    if (variant == 5) return K_HB;  // Heartbeat: no fields (trailing bytes skipped, pack.rs:551)
-    if (variant != 4) return K_OTHER;
+    if constexpr (!G::kTo) {
+        if (variant == 5) return K_HB;  // Heartbeat: no fields (trailing bytes skipped, pack.rs:551)
+    }
+    if (variant != G::kRow) return K_OTHER;
     // wholly in the image (word reads reach at most 7 bytes past the message: the 16 spare
     // bytes after the image cover them)
     if (lim - s.t0 > s.nlds || q >= lim) return K_OTHER | C_UPD;
     uint64_t id;
     if (dvar(ls, q, lim, id) || q >= lim) return K_OTHER | C_UPD;
+    if constexpr (G::kTo) {
+        if (ls.byte(q++) > 1u || q >= lim) return K_OTHER | C_UPD;
+    }
     const uint32_t t = ls.byte(q++);
     const int n = fix_bytes(t);
     uint32_t k = K_OTHER;
@@ -782,8 +826,27 @@ NXG_DEV void put_row(const ColsDesc& cols, DevStatus* st, uint64_t row, uint64_t
     }
 }
 
+// What follows a row's value, which ends at q. From: nothing. To: the Write's bool (read before
+// the value) and its #[pack(default)] WriteId go to wflags / wid; BufferShort means "absent"
+// (derive lib.rs:392-401), any other error is left to emit_other.
+template <class G>
+NXG_DEV bool row_tail(const LdsSrc& ls, const ColsDesc& cols, uint64_t row, uint32_t reply,
+                      uint64_t q, uint64_t lim) {
+    if constexpr (G::kTo) {
+        uint64_t wid = 0;
+        const uint32_t e = dvar(ls, q, lim, wid);
+        if (e && e != E_SHORT) return false;
+        if (row < cols.cap_rows) {
+            cols.wflags[row] = (uint8_t)(reply | (e ? (uint32_t)NXG_WRITE_NO_WID : 0u));
+            cols.wid[row] = e ? 0ull : wid;
+        }
+    }
+    return true;
+}
+
 // Fast decode of one Update of class k at pos; false = not accepted (the caller falls back to
 // emit_other, which reports any error exactly).
+template <class G>
 NXG_DEV bool emit_fast(uint32_t k, const Src& s, const ColsDesc& cols, DevStatus* st,
                        uint64_t pos, uint64_t row, uint64_t child) {
     const LdsSrc ls{s.lds, s.t0};
@@ -791,20 +854,22 @@ NXG_DEV bool emit_fast(uint32_t k, const Src& s, const ColsDesc& cols, DevStatus
     dvar(ls, q, s.W, L);
     const uint64_t take = L - vl64(L);
     const uint64_t lim = take < s.W - q ? q + take : s.W;
-    q++;  // variant 4
+    q++;  // the row variant
     dvar(ls, q, lim, id);
+    uint32_t reply = 0;
+    if constexpr (G::kTo) reply = ls.byte(q++);  // 0 or 1 (classify)
     const uint32_t t = ls.byte(q++);
     if (k == K_FIX) {
         const int n = fix_bytes(t);
         put_row(cols, st, row, id, t == 17 ? 16u : t, fix_value(ls, t, q, n), 0);
-        return true;
+        return row_tail<G>(ls, cols, row, reply, q + n, lim);
     }
     if (k == K_TEXT) {
         uint64_t n;
         if (dvar(ls, q, lim, n) || n > lim - q) return false;
         if (t != 13 && !utf8_ok(ls, q, n)) return false;
         put_row(cols, st, row, id, t, q, (uint32_t)n);
-        return true;
+        return row_tail<G>(ls, cols, row, reply, q + n, lim);
     }
     if (k == K_TIME) {
         uint64_t secs, v2;
@@ -820,7 +885,7 @@ NXG_DEV bool emit_fast(uint32_t k, const Src& s, const ColsDesc& cols, DevStatus
             ns %= 1000000000u;
         }
         put_row(cols, st, row, id, t, secs, ns);
-        return true;
+        return row_tail<G>(ls, cols, row, reply, q, lim);
     }
     if (k == K_VAR) {
         uint64_t v;
@@ -832,7 +897,7 @@ NXG_DEV bool emit_fast(uint32_t k, const Src& s, const ColsDesc& cols, DevStatus
             x = (uint64_t)(int64_t)((int32_t)(u >> 1) ^ (int32_t)(0u - (u & 1u)));
         } else if (t == 7) x = (v >> 1) ^ (0ull - (v & 1ull));
         put_row(cols, st, row, id, t, x, 0);
-        return true;
+        return row_tail<G>(ls, cols, row, reply, q, lim);
     }
     // K_ARR: the elements were checked by classify
     uint64_t cnt;
@@ -851,7 +916,7 @@ NXG_DEV bool emit_fast(uint32_t k, const Src& s, const ColsDesc& cols, DevStatus
         }
         q += n;
     }
-    return true;
+    return row_tail<G>(ls, cols, row, reply, q, lim);
 }
 
 // A Heartbeat at pos (validated by classify): its control-message columns.
@@ -888,20 +953,28 @@ NXG_DEV void fix_push(uint64_t* fix, uint64_t tb, uint64_t te, uint64_t row, uin
 
 // the general path for one message: decode_msg writes the row / children; the control columns
 // and the id are written here (as the per-lane path does)
+template <class G>
 NXG_DEV uint32_t emit_other(const Src& s, const Sink& sink, const ColsDesc& cols, DevStatus* st,
                             uint64_t pos, uint64_t row, uint64_t ctl, uint64_t child) {
     MsgInfo mi;
     uint32_t work = 0;
     uint64_t cn = child;
     const DMode md{0xffffffffu, 0, 1};
-    const uint32_t err = decode_msg<true>(s, pos, mi, &sink, row, cn, work, md);
+    const uint32_t err = decode_msg<true, G>(s, pos, mi, &sink, row, cn, work, md);
     if (err) {
         atomicMax((unsigned long long*)&st->err_key, (unsigned long long)err_key(pos, err));
         return 0;
     }
-    if (mi.variant == 4) {
-        if (row < cols.cap_rows) cols.id[row] = mi.id;
-        else atomicOr(&st->capacity, 1u);
+    if (mi.variant == G::kRow) {
+        if (row < cols.cap_rows) {
+            cols.id[row] = mi.id;
+            if constexpr (G::kTo) {
+                cols.wflags[row] = (uint8_t)mi.wflags;
+                cols.wid[row] = mi.wid;
+            }
+        } else {
+            atomicOr(&st->capacity, 1u);
+        }
     } else if (!cols.ctl_row) {
         atomicOr(&st->nonf64, 1u);
     } else if (ctl < cols.cap_ctl) {
@@ -917,6 +990,7 @@ NXG_DEV uint32_t emit_other(const Src& s, const Sink& sink, const ColsDesc& cols
 
 // The per-lane path (tiles the bucketed path does not take): each lane decodes its messages in
 // order with decode_msg.
+template <class G>
 NXG_DEV void emit_tile_lanes(const Src& s, const Sink& sink, const ColsDesc& cols, DevStatus* st,
                              uint32_t lw, uint64_t c, uint64_t& row, uint64_t& ctl,
                              uint64_t& child, uint32_t& hb) {
@@ -949,16 +1023,23 @@ NXG_DEV void emit_tile_lanes(const Src& s, const Sink& sink, const ColsDesc& col
 #pragma unroll 1
         while (pos < stop) {
             MsgInfo mi;
-            const uint32_t err = decode_msg<true>(s, pos, mi, &sink, myrow, cn, work, md);
+            const uint32_t err = decode_msg<true, G>(s, pos, mi, &sink, myrow, cn, work, md);
             if (err) {  // the frame's first error is the earliest of these (and resolve's)
                 atomicMax((unsigned long long*)&st->err_key, (unsigned long long)err_key(pos, err));
                 break;
             }
             if (ph == 1) {
-                hb += mi.variant == 5;
-                if (mi.variant == 4) {
-                    if (myrow < cols.cap_rows) cols.id[myrow] = mi.id;
-                    else atomicOr(&st->capacity, 1u);
+                if constexpr (!G::kTo) hb += mi.variant == 5;
+                if (mi.variant == G::kRow) {
+                    if (myrow < cols.cap_rows) {
+                        cols.id[myrow] = mi.id;
+                        if constexpr (G::kTo) {
+                            cols.wflags[myrow] = (uint8_t)mi.wflags;
+                            cols.wid[myrow] = mi.wid;
+                        }
+                    } else {
+                        atomicOr(&st->capacity, 1u);
+                    }
                     myrow++;
                 } else if (!cols.ctl_row) {
                     atomicOr(&st->nonf64, 1u);
@@ -983,6 +1064,7 @@ NXG_DEV void emit_tile_lanes(const Src& s, const Sink& sink, const ColsDesc& col
 
 }  // namespace
 
+template <class G>
 __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4))) void nxg_gen_emit_kernel(
     const uint8_t* __restrict__ wire, uint64_t W, uint64_t nt, const uint32_t* __restrict__ lws,
     const uint64_t* __restrict__ base, ColsDesc cols, DevStatus* __restrict__ st,
@@ -1061,7 +1143,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4))) void n
         for (uint32_t m0 = 0; m0 < nmsg; m0 += 64) {
             const uint32_t m = m0 + lane;
             const bool in = m < nmsg;
-            const uint32_t cw = in ? classify(s, t0 + T.mpos[m]) : (uint32_t)K_OTHER;
+            const uint32_t cw = in ? classify<G>(s, t0 + T.mpos[m]) : (uint32_t)K_OTHER;
             const uint32_t k = cw & 15u;
             const bool upd = cw & C_UPD;
             const uint32_t kids = cw >> 8;
@@ -1117,8 +1199,8 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4))) void n
                 const uint32_t m = T.bucket[i];
                 const uint64_t pos = t0 + T.mpos[m];
                 if (kk == K_HB) emit_hb(s, cols, st, pos, row_t + T.cb[m], ctl_t + T.ridx[m]);
-                else fail |= !emit_fast((uint32_t)kk, s, cols, st, pos, row_t + T.ridx[m],
-                                        child_t + T.cb[m]);
+                else fail |= !emit_fast<G>((uint32_t)kk, s, cols, st, pos, row_t + T.ridx[m],
+                                           child_t + T.cb[m]);
             }
         }
         if (__any(fail)) fix_push(fix, t, t + 1, row_t, ctl_t, child_t);  // exact errors there
@@ -1129,6 +1211,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4))) void n
 }
 
 // Re-emits the work list's tiles with the per-lane path (every message through decode_msg).
+template <class G>
 __global__ __launch_bounds__(TPB) void nxg_gen_fix_kernel(
     const uint8_t* __restrict__ wire, uint64_t W, const uint32_t* __restrict__ lws, ColsDesc cols,
     DevStatus* __restrict__ st, const uint64_t* __restrict__ fix) {
@@ -1153,7 +1236,7 @@ __global__ __launch_bounds__(TPB) void nxg_gen_fix_kernel(
             g_load(g, wire, t0, W, lane);
             g_stage(buf, g, lane);
             const Src s = g_src(buf, wire, t0, W);
-            emit_tile_lanes(s, sink, cols, st, lws[t * 64 + lane], t0 + (uint64_t)lane * CH, row,
+            emit_tile_lanes<G>(s, sink, cols, st, lws[t * 64 + lane], t0 + (uint64_t)lane * CH, row,
                             ctl, child, hb);
         }
     }
@@ -1169,7 +1252,7 @@ uint64_t nxg_dec_gen_scratch_bytes(uint64_t W) {
 
 hipError_t nxg_launch_dec_gen(const uint8_t* wire, uint64_t W, const ColsDesc& cd, uint32_t* lws,
                               uint64_t* runs, uint64_t* base, int wgs, DevStatus* st,
-                              hipStream_t s) {
+                              hipStream_t s, bool to) {
     const uint64_t nt = nxg_dec_gen_tiles(W);
     if (nt == 0) return hipSuccess;
     if (wgs <= 0 || wgs * WAVES > gdec2::MAX_RUNS) return hipErrorInvalidValue;
@@ -1178,21 +1261,33 @@ hipError_t nxg_launch_dec_gen(const uint8_t* wire, uint64_t W, const ColsDesc& c
     if (g > (uint64_t)wgs) g = wgs;
     const uint32_t R = (uint32_t)g * WAVES;
     uint64_t* fix = reinterpret_cast<uint64_t*>(lws + 64 * nt);  // nxg_dec_gen_scratch_bytes
-    hipLaunchKernelGGL(nxg_gen_count_kernel, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws, runs, st,
+    if (to) {  // a To frame (Writes): mixed columns with wflags / wid
+        if (!cd.tag || !cd.ctl_row || !cd.wflags || !cd.wid) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(nxg_gen_count_kernel<ToG>, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws,
+                           runs, st, nxg_take_zero_slot(), fix);
+        hipLaunchKernelGGL(nxg_gen_resolve_kernel<ToG>, dim3(1), dim3(RES_TPB), 0, s, wire, W, nt, R,
+                           lws, runs, base, st);
+        hipLaunchKernelGGL(nxg_gen_emit_kernel<ToG>, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws, base,
+                           cd, st, fix);
+        hipLaunchKernelGGL(nxg_gen_fix_kernel<ToG>, dim3(g), dim3(TPB), 0, s, wire, W, lws, cd, st,
+                           fix);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(nxg_gen_count_kernel<FromG>, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws, runs, st,
                        nxg_take_zero_slot(), fix);
-    hipLaunchKernelGGL(nxg_gen_resolve_kernel, dim3(1), dim3(RES_TPB), 0, s, wire, W, nt, R, lws,
+    hipLaunchKernelGGL(nxg_gen_resolve_kernel<FromG>, dim3(1), dim3(RES_TPB), 0, s, wire, W, nt, R, lws,
                        runs, base, st);
-    hipLaunchKernelGGL(nxg_gen_emit_kernel, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws, base, cd,
+    hipLaunchKernelGGL(nxg_gen_emit_kernel<FromG>, dim3(g), dim3(TPB), 0, s, wire, W, nt, lws, base, cd,
                        st, fix);
-    hipLaunchKernelGGL(nxg_gen_fix_kernel, dim3(g), dim3(TPB), 0, s, wire, W, lws, cd, st, fix);
+    hipLaunchKernelGGL(nxg_gen_fix_kernel<FromG>, dim3(g), dim3(TPB), 0, s, wire, W, lws, cd, st, fix);
     return hipGetLastError();
 }
 
 int nxg_dec_gen_wgs(int ncu) {
     int a = 0, b = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, nxg_gen_count_kernel, TPB, 0) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, nxg_gen_count_kernel<FromG>, TPB, 0) !=
             hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, nxg_gen_emit_kernel, TPB, 0) !=
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, nxg_gen_emit_kernel<FromG>, TPB, 0) !=
             hipSuccess)
         return ncu;
     // the passes share the run partition, so one grid for both; neither waits on another

@@ -25,6 +25,14 @@
 // (<Vec<BatchItem> as Pack>::encode, pack.rs:941-952; BatchItem logfile/mod.rs:188-205): each row
 // is varint(Id as u32) and its Event -- the byte 0x40 for Unsubscribed (tag 0x40), else the bare
 // Value -- after the count varint the host writes at [0, arch_base). No length prefix, no variant.
+//
+// Write mode (the rows kernel's template parameter WR, nxg_encode_writes): the subscriber's
+// queue_send(&To::Write(id, reply, value, wid)) loop (netidx/src/subscriber/connection.rs:384-399;
+// To: netidx-netproto/src/publisher.rs:50-70). Each row becomes
+//     varint(L) 02 varint(id) reply Value varint(wid)   L = lw(1 + vl(id) + 1 + |Value| + vl(wid))
+// with reply = wflags & NXG_WRITE_REPLY (bool: pack.rs:1491-1497) and the WriteId always written.
+// The control spans are pre-encoded Subscribe / Unsubscribe messages. No frame-cut bookkeeping
+// (note_split): the host refuses a write batch longer than MAX_BATCH.
 #include "nxg_device.h"
 
 #ifndef NXG_ENC_SKIP
@@ -410,6 +418,7 @@ NXG_DEV uint64_t ctl_upto(const uint64_t* ctl_row, uint64_t n_ctl, uint64_t r) {
 
 // Row r's message length exactly as the rows kernel sizes it (0 for a row whose value errs:
 // that tile reports the error itself).
+template <bool WR>
 NXG_DEV uint64_t row_msg_len(const ColsDesc& c, uint64_t r, bool arch, WalkStack* stk) {
     const Slot v = get_slot(c, true, r);
     uint64_t vlen = 0;
@@ -433,7 +442,9 @@ NXG_DEV uint64_t row_msg_len(const ColsDesc& c, uint64_t r, bool arch, WalkStack
     default: gen = true; break;
     }
     one_lane_at_a_time(gen, [&] { vlen = value_len(c, true, r, &err, stk); });
-    const uint64_t ml = err ? 0ull : arch ? vl64((uint32_t)c.id[r]) + vlen : lwlen(1 + vl64(c.id[r]) + vlen);
+    uint64_t ml;
+    if constexpr (WR) ml = err ? 0ull : lwlen(1 + vl64(c.id[r]) + 1 + vlen + vl64(c.wid[r]));
+    else ml = err ? 0ull : arch ? vl64((uint32_t)c.id[r]) + vlen : lwlen(1 + vl64(c.id[r]) + vlen);
     if (!err && ml > (arch ? 0xFFFFFFFFull : 0x3FFFFFFFull)) return 0;
     return ml;
 }
@@ -455,7 +466,11 @@ __global__ __launch_bounds__(TPB) void nxg_enc_ctl_scan_kernel(ColsDesc c, uint6
     if (threadIdx.x == 0) ctl_pre[c.n_ctl] = carry;
 }
 
-__global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
+// The rows kernel's body. WR: Write mode (To::Write rows from c.wflags / c.wid; arch_base is 0).
+// (In the unnamed namespace, so that each instantiation's LDS arrays stay internal to its kernel.)
+namespace {
+template <bool WR>
+NXG_DEV void enc_rows(
     ColsDesc c, const uint8_t* __restrict__ heap, uint8_t* __restrict__ out, uint64_t cap,
     const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
     uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
@@ -465,7 +480,10 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
     __shared__ uint64_t tmp[4];
     __shared__ uint64_t sh_base;
     __shared__ __attribute__((aligned(16))) uint8_t stg[GSTG];
-    __shared__ uint32_t cls_n[NCLS], cls_b[NCLS + 1];
+#if !NXG_ENC_CLS2
+    __shared__ uint32_t cls_n[NCLS];
+#endif
+    __shared__ uint32_t cls_b[NCLS + 1];
     __shared__ uint32_t cls_w[TPB / 64][NCLS];  // per wave: class counts, then first entries
     __shared__ uint16_t lst_row[GTILE];  // the tile's rows sorted by value class
     __shared__ uint16_t off_lds[GTILE];  // staging offset per row (tile-local index)
@@ -579,7 +597,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
         const uint32_t ne = cls_b[NCLS];
         // 2. message lengths, class by class. Each thread's next entry's slot and id are loaded
         //    while it sizes the current one (NXG_ENC_PF: two memory round trips in flight)
-        auto size_one = [&](uint32_t rl, Slot v, uint64_t idv) {
+        auto size_one = [&](uint32_t rl, Slot v, uint64_t idv, uint64_t widv, uint32_t) {
             const uint64_t r = rt + rl;
             uint64_t vlen = 0;
             uint32_t err = 0;
@@ -610,9 +628,14 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
             one_lane_at_a_time(gen, [&] { vlen = value_len(c, true, r, &err, stk); });
             // queue_send refuses a message longer than MAX_BATCH (channel.rs:178-181); that bound
             // also keeps the 32-bit staged lengths exact
-            const uint64_t ml = err    ? 0ull
-                                : arch ? vl64((uint32_t)idv) + vlen
-                                       : lwlen(1 + vl64(idv) + vlen);
+            uint64_t ml;
+            if constexpr (WR) {
+                ml = err ? 0ull : lwlen(1 + vl64(idv) + 1 + vlen + vl64(widv));
+            } else {
+                ml = err    ? 0ull
+                     : arch ? vl64((uint32_t)idv) + vlen
+                            : lwlen(1 + vl64(idv) + vlen);
+            }
             if (!err && ml > (arch ? 0xFFFFFFFFull : 0x3FFFFFFFull)) err = NXG_TOO_BIG;
             if (err) atomicMax(&st->err_kind, err);
             len_lds[rl] = err ? 0u : (uint32_t)ml;
@@ -621,18 +644,26 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
         uint32_t k_rl[4];
         Slot k_v[4];
         uint64_t k_id[4];
+        uint64_t k_w[4];  // WR: the rows' WriteIds
+        uint32_t k_f[4];  // WR: and flags
 #pragma unroll
         for (int j = 0; j < GRPT; j++) {
             const uint32_t e = tid + (uint32_t)j * TPB;
             k_rl[j] = e < ne ? lst_row[e] : 0u;
             k_v[j] = e < ne ? get_slot(c, true, rt + k_rl[j]) : Slot{0, 0, 0};
             k_id[j] = e < ne ? c.id[rt + k_rl[j]] : 0ull;
+            k_w[j] = 0ull;
+            k_f[j] = 0u;
+            if constexpr (WR) {
+                k_w[j] = e < ne ? c.wid[rt + k_rl[j]] : 0ull;
+                k_f[j] = e < ne ? c.wflags[rt + k_rl[j]] : 0u;
+            }
         }
         // (spelled out: a loop the compiler leaves rolled would index the arrays dynamically,
         // i.e. put them in scratch memory)
         static_assert(GRPT <= 4, "NXG_ENC_KEEP keeps at most 4 rows per thread");
 #define NXG_KEEP_CALL(F, j) \
-    if ((j) < GRPT && tid + (uint32_t)(j) * TPB < ne) F(k_rl[j], k_v[j], k_id[j])
+    if ((j) < GRPT && tid + (uint32_t)(j) * TPB < ne) F(k_rl[j], k_v[j], k_id[j], k_w[j], k_f[j])
         NXG_KEEP_CALL(size_one, 0);
         NXG_KEEP_CALL(size_one, 1);
         NXG_KEEP_CALL(size_one, 2);
@@ -656,7 +687,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                     p_v = get_slot(c, true, rt + p_rl);
                     p_id = c.id[rt + p_rl];
                 }
-                size_one(rl, v, idv);
+                size_one(rl, v, idv, WR ? c.wid[rt + rl] : 0ull, 0u);
             }
         }
 #endif
@@ -692,7 +723,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                         const uint64_t q0 = t * GTILE;
                         uint64_t b = 0;
                         for (uint64_t r = q0 + lane; r < q0 + GTILE && r < n; r += 64)
-                            b += row_msg_len(c, r, arch, &wstk[0]);
+                            b += row_msg_len<WR>(c, r, arch, &wstk[0]);
                         return wave_sum<uint64_t>(b);
                     });
 #endif
@@ -712,12 +743,17 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                 }
             }
             __syncthreads();
-            auto stage_one = [&](uint32_t rl, Slot v, uint64_t idv) {
+            auto stage_one = [&](uint32_t rl, Slot v, uint64_t idv, uint64_t widv, uint32_t fl) {
                 const uint64_t r = rt + rl;
                 const uint32_t len = len_lds[rl];
                 if (!len) return;
                 Out w{stg, off_lds[rl]};
-                if (arch) {
+                if constexpr (WR) {
+                    w.var(len);
+                    w.b(2);
+                    w.var(idv);
+                    w.b(fl & 1u);
+                } else if (arch) {
                     w.var((uint32_t)idv);
                 } else {
                     w.var(len);
@@ -745,6 +781,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                 }
                 one_lane_at_a_time(cls_lds[rl] == CLS_GEN,
                                    [&] { value_write(c, heap, true, r, w, stk); });
+                if constexpr (WR) w.var(widv);
             };
 #if NXG_ENC_KEEP
             NXG_KEEP_CALL(stage_one, 0);
@@ -770,7 +807,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                     q_v = get_slot(c, true, rt + q_rl);
                     q_id = c.id[rt + q_rl];
                 }
-                stage_one(rl, v, idv);
+                stage_one(rl, v, idv, WR ? c.wid[rt + rl] : 0ull, WR ? c.wflags[rt + rl] : 0u);
             }
 #endif
         }
@@ -790,7 +827,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
             // 4b. the staging out as aligned nontemporal 16-byte stores: global block g holds the
             //     staged bytes from g - tbase; the two edge blocks (shared with the neighbours)
             //     by bytes
-            if (!arch && tbase <= kMaxBatch && kMaxBatch < tbase + tot) {
+            if (!WR && !arch && tbase <= kMaxBatch && kMaxBatch < tbase + tot) {
                 uint64_t o = tbase + off;
 #pragma unroll
                 for (int k = 0; k < GRPT; k++) {
@@ -837,12 +874,17 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                 if (r < n && Lk && out) {
                     uint64_t pos = rpos;
                     if (c.n_ctl) pos += ctl_pre[ctl_upto(c.ctl_row, c.n_ctl, r)];
-                    if (!arch) note_split(st, pos, Lk);
+                    if (!WR && !arch) note_split(st, pos, Lk);
                     if (pos + Lk > cap) {
                         atomicOr(&st->capacity, 1u);
                     } else {
                         Out w{out, pos};
-                        if (arch) {
+                        if constexpr (WR) {
+                            w.var(Lk);
+                            w.b(2);
+                            w.var(c.id[r]);
+                            w.b(c.wflags[r] & 1u);
+                        } else if (arch) {
                             w.var((uint32_t)c.id[r]);
                         } else {
                             w.var(Lk);
@@ -852,6 +894,7 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
                         if (cls_lds[tid * GRPT + k] != CLS_GEN) row_write_flat(c, heap, get_slot(c, true, r), w);
                         one_lane_at_a_time(cls_lds[tid * GRPT + k] == CLS_GEN,
                                            [&] { value_write(c, heap, true, r, w, stk); });
+                        if constexpr (WR) w.var(c.wid[r]);
                     }
                 }
                 rpos += Lk;
@@ -864,6 +907,24 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
         ESTAMP(6);
         __syncthreads();
     }
+}
+}  // namespace
+
+__global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
+    ColsDesc c, const uint8_t* __restrict__ heap, uint8_t* __restrict__ out, uint64_t cap,
+    const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
+    uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
+    DevStatus* zst, uint64_t arch_base, uint32_t patience) {
+    enc_rows<false>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst, arch_base,
+                    patience);
+}
+__global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_writes_kernel(
+    ColsDesc c, const uint8_t* __restrict__ heap, uint8_t* __restrict__ out, uint64_t cap,
+    const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
+    uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
+    DevStatus* zst, uint64_t arch_base, uint32_t patience) {
+    enc_rows<true>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst, arch_base,
+                   patience);
 }
 
 __global__ __launch_bounds__(TPB) void nxg_enc_ctl_write_kernel(
@@ -900,7 +961,7 @@ extern "C" int nxg_debug_enc_stamps(unsigned long long* out) {
 hipError_t nxg_launch_enc_general(const ColsDesc& cd, const uint8_t* heap, uint8_t* out,
                                   uint64_t cap, uint64_t* scratch, uint64_t* tstat,
                                   uint32_t epoch, DevStatus* st, int grid, hipStream_t s,
-                                  uint64_t arch_base) {
+                                  uint64_t arch_base, bool writes) {
     // scratch layout: ctl_pre[n_ctl + 1] | row_off[n_rows]  (only when n_ctl > 0)
     uint64_t* ctl_pre = scratch;
     uint64_t* row_off = cd.n_ctl ? scratch + cd.n_ctl + 1 : nullptr;
@@ -908,9 +969,16 @@ hipError_t nxg_launch_enc_general(const ColsDesc& cd, const uint8_t* heap, uint8
     const uint64_t nt = nxg_enc_general_tiles(cd.n_rows);
     if (nt) {
         const uint64_t g = grid <= 0 ? nt : (nt < (uint64_t)grid ? nt : (uint64_t)grid);
-        hipLaunchKernelGGL(nxg_enc_rows_kernel, dim3(g), dim3(TPB), 0, s, cd, heap, out, cap,
-                           cd.n_ctl ? ctl_pre : nullptr, row_off, tstat, (uint32_t)nt, epoch, st, nxg_take_zero_slot(),
-                           arch_base, nxg_patience);
+        if (writes) {
+            if (arch_base || !cd.wflags || !cd.wid) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(nxg_enc_rows_writes_kernel, dim3(g), dim3(TPB), 0, s, cd, heap, out,
+                               cap, cd.n_ctl ? ctl_pre : nullptr, row_off, tstat, (uint32_t)nt,
+                               epoch, st, nxg_take_zero_slot(), (uint64_t)0, nxg_patience);
+        } else {
+            hipLaunchKernelGGL(nxg_enc_rows_kernel, dim3(g), dim3(TPB), 0, s, cd, heap, out,
+                               cap, cd.n_ctl ? ctl_pre : nullptr, row_off, tstat, (uint32_t)nt,
+                               epoch, st, nxg_take_zero_slot(), arch_base, nxg_patience);
+        }
     }
     if (cd.n_ctl && out) {
         const uint64_t nb = (cd.n_ctl + TPB - 1) / TPB;

@@ -160,18 +160,21 @@ hipError_t nxg_launch_partition(const uint8_t* tag, const uint64_t* fixed, const
                                 hipStream_t s);
 uint64_t nxg_enc_general_tiles(uint64_t n);  // tiles (and tstat words) of a general encode
 // arch_base > 0: archive-batch rows after an arch_base-byte count header (nxg_encode_general.hip)
+// writes: To::Write rows from cols.wflags / cols.wid (nxg_encode_writes; arch_base 0)
 hipError_t nxg_launch_enc_general(const ColsDesc& cols, const uint8_t* heap, uint8_t* out,
                                   uint64_t cap, uint64_t* scratch, uint64_t* tstat,
                                   uint32_t epoch, DevStatus* st, int grid, hipStream_t s,
-                                  uint64_t arch_base = 0);
+                                  uint64_t arch_base = 0, bool writes = false);
 // general decode: count + resolve + emit + fix. `lws` holds nxg_dec_gen_scratch_bytes(W) bytes
 // (64 u32 lane words per tile, then the emit pass's work list), `runs` gdec2::MAX_RUNS *
 // RUN_WORDS u64, `base` gdec2::MAX_RUNS * 4 u64; none needs zeroing.
 uint64_t nxg_dec_gen_tiles(uint64_t W);
 uint64_t nxg_dec_gen_scratch_bytes(uint64_t W);
+// to: the frame is a To stream (nxg_decode_writes); `cols` then needs the mixed layout and
+// wflags / wid.
 hipError_t nxg_launch_dec_gen(const uint8_t* wire, uint64_t W, const ColsDesc& cols, uint32_t* lws,
                               uint64_t* runs, uint64_t* base, int wgs, DevStatus* st,
-                              hipStream_t s);
+                              hipStream_t s, bool to = false);
 int nxg_dec_gen_wgs(int ncu);
 // fast mixed decode (nxg_decode_mixed.hip): frames of Update messages shorter than 128 bytes with
 // flat values; sets fast_fail for anything else. `scratch`: nxg_fmx_scratch_bytes(W), no zeroing.
@@ -284,4 +287,7 @@ struct ColsDesc {
     uint64_t* ctl_off;
     uint32_t* ctl_len;
     uint8_t* ctl_variant;
+    // To::Write rows (NxgWriteCols): NxgWriteFlags and the WriteId per row; null for From
+    uint8_t* wflags;
+    uint64_t* wid;
 };

@@ -1,9 +1,13 @@
-// nxg_msg.h -- device-side decoder of one publisher::From message (general path).
+// nxg_msg.h -- device-side decoder of one publisher::From or publisher::To message (general
+// path). The message grammar is a compile-time parameter (FromG, ToG below): the length wrap, the
+// Value decoder and the three decode modes are shared, only the variants and their fields differ.
 //
 // A per-lane restatement of:
 //   len_wrapped_decode         netidx-core/src/pack.rs:537-555
 //   derived enum decode        netidx-derive/src/lib.rs:482-601 (From, publisher.rs:73-96;
 //                              #[pack(default)] WriteId per lib.rs:392-401)
+//   publisher::To              netidx-netproto/src/publisher.rs:50-70; SocketAddr pack.rs:187-238,
+//                              Bytes pack.rs:251-258, bool pack.rs:1491-1497
 //   Value::decode              netidx-value/src/lib.rs:470-506
 //   ValArray / Map / PBytes / ArcStr / DateTime / Duration / Decimal / Abstract decoders
 //                              array.rs:595-612, pack.rs:1225-1239, pbuf.rs:139-147,
@@ -508,13 +512,77 @@ struct MsgInfo {
     uint64_t next;
     uint32_t variant;
     uint64_t id;
+    uint32_t wflags;  // To::Write: NXG_WRITE_* bits
+    uint64_t wid;     // To::Write: the WriteId (0 when absent)
 };
 
-// The message body after its length prefix: variant byte and fields, from source s.
+// The message grammars. kRow: the variant whose (Id, Value) become a row; kMinRow: the smallest
+// length byte of such a message (Update 04 04 00 10, Write 05 02 00 00 10); kMaxVariant: the
+// last known variant; kPath: NxgStatus.path of the general decode.
+struct FromG {
+    static constexpr bool kTo = false;
+    static constexpr uint32_t kRow = 4, kMinRow = 4, kMaxVariant = 6, kPath = 2;
+};
+struct ToG {
+    static constexpr bool kTo = true;
+    static constexpr uint32_t kRow = 2, kMinRow = 5, kMaxVariant = 2, kPath = NXG_PATH_WRITES;
+};
+
+// publisher::To after its length prefix (publisher.rs:50-70). Subscribe and Unsubscribe are
+// validated only; a Write's value goes to row `row`, its bool and WriteId to info.
 template <bool EMIT, class S>
+NXG_DEV uint32_t decode_body_to(const S& s, uint64_t p, uint64_t lim, MsgInfo& info,
+                                const Sink* k, uint64_t row, uint64_t& child_next,
+                                uint32_t& work, const DMode& md) {
+    if (p >= lim) return E_SHORT;
+    const uint32_t variant = s.byte(p++);
+    info.variant = variant;
+    uint64_t v, off, len;
+    uint32_t e;
+    switch (variant) {
+    case 0: {  // Subscribe { path, resolver, timestamp, permissions, token }
+        if ((e = dstr(s, p, lim, true, off, len, work, md))) return e;
+        if (p >= lim) return E_SHORT;
+        const uint32_t at = s.byte(p++);  // SocketAddr: 0 = V4 (4 + 2), 1 = V6 (16 + 2 + 4 + 4)
+        if (at > 1u) return E_UNKNOWN_TAG;
+        const uint64_t need = (at ? 26u : 6u) + 8u + 4u;  // + timestamp u64 + permissions u32
+        if (lim - p < need) return E_SHORT;
+        p += need;
+        if ((e = dvar(s, p, lim, v))) return e;  // token: Bytes
+        return v > lim - p ? E_TOO_BIG : E_OK;
+    }
+    case 1:  // Unsubscribe(Id)
+        return dvar(s, p, lim, v);
+    case 2:  // Write(Id, bool, Value, #[pack(default)] WriteId)
+        break;
+    default:
+        return E_UNKNOWN_TAG;
+    }
+    if ((e = dvar(s, p, lim, v))) return e;
+    info.id = v;
+    if (p >= lim) return E_SHORT;
+    const uint32_t reply = s.byte(p++);
+    if (reply > 1u) return E_UNKNOWN_TAG;
+    uint64_t cn = child_next;
+    e = dvalue<EMIT>(s, p, lim, k, true, row, cn, work, md);
+    child_next = cn;
+    if (e) return e;
+    // BufferShort here (a truncated varint included) means "no WriteId" (derive lib.rs:392-401)
+    uint64_t wid = 0;
+    e = dvar(s, p, lim, wid);
+    if (e && e != E_SHORT) return e;
+    if (md.spec && p != lim) return E_INVALID;  // exact fit (see decode_msg)
+    info.wflags = reply | (e ? (uint32_t)NXG_WRITE_NO_WID : 0u);
+    info.wid = e ? 0ull : wid;
+    return E_OK;
+}
+
+// The message body after its length prefix: variant byte and fields, from source s.
+template <bool EMIT, class G = FromG, class S>
 NXG_DEV uint32_t decode_body(const S& s, uint64_t p, uint64_t lim, MsgInfo& info, const Sink* k,
                              uint64_t row, uint64_t& child_next, uint32_t& work,
                              const DMode& md) {
+    if constexpr (G::kTo) return decode_body_to<EMIT>(s, p, lim, info, k, row, child_next, work, md);
     if (p >= lim) return E_SHORT;
     const uint32_t variant = s.byte(p++);
     info.variant = variant;
@@ -562,7 +630,7 @@ NXG_DEV uint32_t decode_body(const S& s, uint64_t p, uint64_t lim, MsgInfo& info
 // length-wrapped region (trailing bytes skipped, pack.rs:551-553). Update values are written
 // to row `row` (EMIT with md.write); their children are allocated from child_next. The values
 // inside control messages (Subscribed, WriteResult) are validated, not written.
-template <bool EMIT>
+template <bool EMIT, class G = FromG>
 NXG_DEV uint32_t decode_msg(const Src& s, uint64_t pos, MsgInfo& info, const Sink* k,
                             uint64_t row, uint64_t& child_next, uint32_t& work, const DMode& md) {
     const LdsSrc ls{s.lds, s.t0};
@@ -581,25 +649,28 @@ NXG_DEV uint32_t decode_msg(const Src& s, uint64_t pos, MsgInfo& info, const Sin
     const uint64_t lim = take < s.W - p ? p + take : s.W;
     info.next = lim;
     if (img && lim - s.t0 <= s.nlds)
-        return decode_body<EMIT>(ls, p, lim, info, k, row, child_next, work, md);
-    return decode_body<EMIT>(gs, p, lim, info, k, row, child_next, work, md);
+        return decode_body<EMIT, G>(ls, p, lim, info, k, row, child_next, work, md);
+    return decode_body<EMIT, G>(gs, p, lim, info, k, row, child_next, work, md);
 }
 
 // ---- structure only (the general decoder's count pass) ---------------------------------------
 // Message boundaries depend only on the length prefixes (len_wrapped_decode, pack.rs:537-555),
-// so the count pass reads just the prefix, the variant and, for an Update whose value is a
-// container, the container structure (to count the child slots the emit pass will allocate).
+// so the count pass reads just the prefix, the variant and, for an Update (a Write) whose value is
+// a container, the container structure (to count the child slots the emit pass will allocate).
 // Content is not validated here: the emit pass decodes every message on the chain and reports
 // the first content error. Only errors in the length prefix, which break the chain, are
 // returned (and E_BUDGET from a bounded container walk).
-template <class S>
+template <class G = FromG, class S>
 NXG_DEV uint32_t skim_body(const S& s, uint64_t p, uint64_t lim, MsgInfo& info,
                            uint64_t& children, uint32_t& work, uint32_t budget) {
     const uint32_t variant = s.byte(p++);
     info.variant = variant;
-    if (variant != 4) return E_OK;
+    if (variant != G::kRow) return E_OK;
     uint64_t v;
     if (dvar(s, p, lim, v) || p >= lim) return E_OK;  // content error: reported by emit
+    if constexpr (G::kTo) {  // the Write's bool, between the id and the value
+        if (++p >= lim) return E_OK;
+    }
     const uint32_t t = s.byte(p);
     if (!is_container(s, t, p + 1, lim)) return E_OK;
     if (t == 19) {  // an array of fixed-size scalars: one child slot per element (as dvalue)
@@ -625,6 +696,7 @@ NXG_DEV uint32_t skim_body(const S& s, uint64_t p, uint64_t lim, MsgInfo& info,
     return e == E_BUDGET ? E_BUDGET : E_OK;
 }
 
+template <class G = FromG>
 NXG_DEV uint32_t skim_msg(const Src& s, uint64_t pos, MsgInfo& info, uint64_t& children,
                           uint32_t& work, uint32_t budget) {
     const LdsSrc ls{s.lds, s.t0};
@@ -640,8 +712,9 @@ NXG_DEV uint32_t skim_msg(const Src& s, uint64_t pos, MsgInfo& info, uint64_t& c
     info.variant = 0xff;  // no variant byte: a content error (BufferShort), reported by emit
     children = 0;
     if (p >= lim) return E_OK;
-    if (img && lim - s.t0 <= s.nlds) return skim_body(ls, p, lim, info, children, work, budget);
-    return skim_body(gs, p, lim, info, children, work, budget);
+    if (img && lim - s.t0 <= s.nlds)
+        return skim_body<G>(ls, p, lim, info, children, work, budget);
+    return skim_body<G>(gs, p, lim, info, children, work, budget);
 }
 
 // the first-error key: the larger key is the earlier (offset, kind); 0 = no error
