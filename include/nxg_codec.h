@@ -518,6 +518,24 @@ bool nxg_archive_decompress(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t*
                             uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
                             uint8_t* dout, uint64_t cap, uint64_t* need, NetidxError* err);
 
+/* replaces compress_task of ArchiveReader::compress (reader.rs:741-769), many records per call:
+ * record i is src[recs[i].off, + recs[i].len), the bytes after its RecordHeader of an uncompressed
+ * archive: the RecordIndex when `indexed` (its first varint is the index's own length), then the
+ * packed batch. Its compressed record -- u32 BE recs[i].len | the index bytes verbatim | one zstd
+ * frame of the batch (Single_Segment with the content size, no checksum, the Dictionary_ID in its
+ * smallest field for a zstd-format dictionary, none for raw content or dict == NULL) -- is written
+ * to out[recs[i].out_off, + recs[i].out_len), the bytes add_batch_raw takes. Slots are disjoint,
+ * in record order and not contiguous: each has its record's worst case, 4 + index + 17 + batch +
+ * 3 per 128 KiB block. recs[i].err: 0, or 7 when the record is shorter than its index prefix (that
+ * record alone fails). The frames are not libzstd's bytes; libzstd and nxg_archive_decompress
+ * turn them back into the batch, and the same record and dictionary give the same bytes in every
+ * call. src and out are host memory; out == NULL: *need = the bytes of all slots, computed on the
+ * host. Synchronous. Returns false on misuse, a HIP failure, cap < *need, or a record of 2^32
+ * bytes or more. */
+bool nxg_archive_compress(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t* src,
+                          uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
+                          uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err);
+
 /* ---- the publisher <-> subscriber connection (BASELINE configs[0]) ------------------------
  * Replaces hello_publisher (netidx/src/subscriber/connection.rs:120-140), ClientCtx::hello
  * (publisher/server.rs:367-381), read_task / flush_buf (channel.rs:107-126, 379-443) and the

@@ -225,6 +225,10 @@ SIGNATURES = {
                                           C.POINTER(NxgArchiveRecord), C.c_uint32, C.c_bool,
                                           C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                           C.POINTER(NetidxError)]),
+    "nxg_archive_compress": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.POINTER(NxgArchiveRecord), C.c_uint32, C.c_bool,
+                                        C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                        C.POINTER(NetidxError)]),
     "nxg_decode_archive_batch": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.POINTER(NxgColumns), C.POINTER(NxgStatus),
                                             C.POINTER(C.c_uint64), C.POINTER(NetidxError)]),
@@ -552,6 +556,27 @@ class Codec:
         _check(lib().nxg_archive_decompress(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs,
                                             n, indexed, C.c_void_p(out.data_ptr()), out.numel(),
                                             C.byref(need), C.byref(err)), err)
+        return out, [(recs[i].out_off, recs[i].out_len, recs[i].err) for i in range(n)]
+
+    def archive_compress(self, src, records, indexed=False, zdict=None):
+        """Uncompressed archive records (host bytes `src`, [(off, len)] after each RecordHeader)
+        compressed on the device (nxg_archive_compress). Returns (host uint8 array,
+        [(out_off, out_len, err)]): record i's compressed record -- u32 BE length | index | zstd
+        frame -- is out[out_off:out_off + out_len]."""
+        b = src if isinstance(src, np.ndarray) else np.frombuffer(bytes(src), np.uint8)
+        b = np.ascontiguousarray(b)
+        n = len(records)
+        recs = (NxgArchiveRecord * max(n, 1))()
+        for i, (o, ln) in enumerate(records):
+            recs[i].off, recs[i].len = o, ln
+        need, err = C.c_uint64(0), NetidxError()
+        dh = zdict.h if zdict else None
+        _check(lib().nxg_archive_compress(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs,
+                                          n, indexed, None, 0, C.byref(need), C.byref(err)), err)
+        out = np.zeros(max(need.value, 1), np.uint8)
+        _check(lib().nxg_archive_compress(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs,
+                                          n, indexed, C.c_void_p(out.ctypes.data), need.value,
+                                          C.byref(need), C.byref(err)), err)
         return out, [(recs[i].out_off, recs[i].out_len, recs[i].err) for i in range(n)]
 
     def decode_batch(self, frame, layout=LAYOUT_MIXED, flags=0, device="cuda"):

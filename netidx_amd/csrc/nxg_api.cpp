@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -137,6 +138,21 @@ struct NxgCtx {
     int zgrid = 0;
     void* zrecs = nullptr;
     size_t zrecs_cap = 0;
+    // zstd compression (nxg_archive_compress): the predefined distributions' encoding tables, the
+    // waves' literal / sequence slabs, descriptors, the frames' slots and their packed copy
+    void* zc_tables = nullptr;
+    uint8_t* zc_slab = nullptr;
+    int zc_grid = 0;
+    uint8_t* zc_recs = nullptr;
+    size_t zc_recs_cap = 0;
+    uint8_t* zc_out = nullptr;
+    size_t zc_out_cap = 0;
+    uint8_t* zc_pack = nullptr;
+    size_t zc_pack_cap = 0;
+    uint8_t* zc_hpin = nullptr;  // pinned host staging of the packed frames
+    size_t zc_hpin_cap = 0;
+    hipEvent_t zc_ev[2] = {nullptr, nullptr};  // around the compressor kernel (diagnostics)
+    float zc_kernel_ms = 0.f;
     DevStatus last{};  // last completed decode's device status (diagnostics)
     uint64_t fa_last[8] = {};  // the last fast archive attempt's FaHead (diagnostics)
     uint64_t last_split = 0;  // last completed encode's DevStatus.split_start
@@ -845,6 +861,14 @@ void nxg_ctx_destroy(NxgCtx* c) {
     if (c->zdefs) (void)hipFree(c->zdefs);
     if (c->zlit) (void)hipFree(c->zlit);
     if (c->zrecs) (void)hipFree(c->zrecs);
+    if (c->zc_tables) (void)hipFree(c->zc_tables);
+    if (c->zc_slab) (void)hipFree(c->zc_slab);
+    if (c->zc_recs) (void)hipFree(c->zc_recs);
+    if (c->zc_out) (void)hipFree(c->zc_out);
+    if (c->zc_pack) (void)hipFree(c->zc_pack);
+    if (c->zc_hpin) (void)hipHostFree(c->zc_hpin);
+    for (hipEvent_t e : c->zc_ev)
+        if (e) (void)hipEventDestroy(e);
     if (c->dheap) (void)hipFree(c->dheap);
     if (c->dwflags) (void)hipFree(c->dwflags);
     if (c->dwid) (void)hipFree(c->dwid);
@@ -1371,6 +1395,13 @@ struct NxgZstdDict {
     int device;
     void* ddev = nullptr;       // NxzDictDev
     uint8_t* content = nullptr;  // the dictionary's content (history before every frame)
+    // encode side (nxg_archive_compress): the Huffman codes of the dictionary's weights, built
+    // with the dictionary; the content's hash table and the device copy, built at first use
+    uint32_t content_len = 0;
+    std::vector<uint8_t> enc_host;  // NxzEncDict
+    void* denc = nullptr;
+    uint32_t* dtable = nullptr;
+    std::mutex enc_mu;
 };
 
 NxgZstdDict* nxg_zstd_dict_new(NxgCtx* c, const uint8_t* dict, uint64_t len, NetidxError* err) {
@@ -1389,6 +1420,13 @@ NxgZstdDict* nxg_zstd_dict_new(NxgCtx* c, const uint8_t* dict, uint64_t len, Net
     NxgZstdDict* d = new NxgZstdDict();
     d->device = c->device;
     const uint64_t clen = len - coff;
+    d->content_len = (uint32_t)clen;
+    d->enc_host.resize(nxg_zstd_enc_dict_bytes());
+    if (!nxg_zstd_build_enc_dict(dict, len, reinterpret_cast<NxzEncDict*>(d->enc_host.data()))) {
+        set_err(err, "not a valid zstd dictionary");
+        delete d;
+        return nullptr;
+    }
     auto fail = [&](hipError_t e) -> NxgZstdDict* {
         set_err(err, "zstd dictionary upload: %s", hipGetErrorString(e));
         nxg_zstd_dict_free(d);
@@ -1410,6 +1448,8 @@ void nxg_zstd_dict_free(NxgZstdDict* d) {
     (void)hipSetDevice(d->device);
     if (d->ddev) (void)hipFree(d->ddev);
     if (d->content) (void)hipFree(d->content);
+    if (d->denc) (void)hipFree(d->denc);
+    if (d->dtable) (void)hipFree(d->dtable);
     delete d;
 }
 
@@ -1524,6 +1564,229 @@ bool nxg_archive_decompress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* s
     }
     return true;
 }
+
+// the dictionary's encode-side device state, at the first compression with it
+static bool zstd_dict_enc_ready(NxgCtx* c, NxgZstdDict* d, NetidxError* err) {
+    std::lock_guard<std::mutex> g(d->enc_mu);
+    if (d->denc) return true;
+    if (d->device != c->device) {
+        set_err(err, "the dictionary belongs to another device");
+        return false;
+    }
+    void* tab = nullptr;
+    void* enc = nullptr;
+    auto fail = [&](hipError_t e) {
+        set_err(err, "zstd dictionary hash table: %s", hipGetErrorString(e));
+        if (tab) (void)hipFree(tab);
+        if (enc) (void)hipFree(enc);
+        return false;
+    };
+    hipError_t e;
+    if ((e = hipMalloc(&tab, nxg_zstd_dict_table_bytes())) != hipSuccess) return fail(e);
+    if ((e = nxg_launch_zstd_dict_hash(d->content, d->content_len, static_cast<uint32_t*>(tab),
+                                       c->stream)) != hipSuccess)
+        return fail(e);
+    nxg_zstd_enc_dict_set(reinterpret_cast<NxzEncDict*>(d->enc_host.data()), d->content,
+                          d->content_len, static_cast<uint32_t*>(tab));
+    if ((e = hipMalloc(&enc, d->enc_host.size())) != hipSuccess) return fail(e);
+    if ((e = hipMemcpyAsync(enc, d->enc_host.data(), d->enc_host.size(), hipMemcpyHostToDevice,
+                            c->stream)) != hipSuccess)
+        return fail(e);
+    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return fail(e);
+    d->dtable = static_cast<uint32_t*>(tab);
+    d->denc = enc;
+    return true;
+}
+
+static bool grow_dev(NxgCtx* c, uint8_t** p, size_t* cap, size_t need, NetidxError* err) {
+    if (*cap >= need) return true;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (*p) HIPCHK(hipFree(*p));
+    *p = nullptr;
+    *cap = 0;
+    const size_t n = std::max<size_t>(need + need / 4, 1 << 16);
+    HIPCHK(hipMalloc(p, n));
+    *cap = n;
+    return true;
+}
+
+bool nxg_archive_compress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* src,
+                          uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
+                          uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err) {
+    if (!c || (n && (!recs || !src))) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (is_device_ptr(src) || (out && is_device_ptr(out))) {
+        set_err(err, "the records and the output must be in host memory");
+        return false;
+    }
+    // the index prefixes and the slots on the host (compress_task, reader.rs:741-769: the index
+    // is copied, the rest is the batch)
+    struct Rec {
+        uint64_t src_off, src_len, out_off, out_cap;
+    };
+    struct Res {
+        uint64_t out_len;
+        uint32_t err, pad;
+    };
+    std::vector<Rec> rd(n);
+    std::vector<uint64_t> ilen(n, 0);
+    uint64_t total = 0, dtotal = 0, lo = ~0ull, hi = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        NxgArchiveRecord& r = recs[i];
+        r.out_len = 0;
+        r.err = 0;
+        r.out_off = total;
+        rd[i] = Rec{0, 0, dtotal, 0};
+        if (r.off > src_len || r.len > src_len - r.off) {
+            set_err(err, "record %u lies outside the source", i);
+            return false;
+        }
+        if (r.len >= (1ull << 32)) {
+            set_err(err, "record %u has 2^32 bytes or more", i);
+            return false;
+        }
+        uint64_t pos = 0;
+        if (indexed) {  // decode_varint (pack.rs:504-520): the index's length, prefix included
+            const uint8_t* p = src + r.off;
+            uint64_t v = 0;
+            bool ok = false;
+            for (uint32_t k = 0; k < 10 && k < r.len; k++) {
+                v |= (uint64_t)(p[k] & 0x7f) << (7 * k);
+                if (p[k] < 0x80) {
+                    ok = true;
+                    break;
+                }
+            }
+            if (!ok || v > r.len) {
+                r.err = 7;
+                continue;
+            }
+            pos = v;
+        }
+        ilen[i] = pos;
+        const uint64_t blen = r.len - pos, fb = nxg_zstd_frame_bound(blen);
+        rd[i] = Rec{r.off + pos, blen, dtotal, fb};
+        lo = std::min(lo, r.off + pos);
+        hi = std::max(hi, r.off + r.len);
+        dtotal += fb;
+        total += 4 + pos + fb;
+    }
+    if (need) *need = total;
+    if (!out) return true;
+    if (total > cap) {
+        set_err(err, "output buffer too small: the records need %llu bytes, capacity %llu",
+                (unsigned long long)total, (unsigned long long)cap);
+        return false;
+    }
+    if (n == 0 || dtotal == 0) return true;
+    if (!set_device(c, err)) return false;
+    if (dict && !zstd_dict_enc_ready(c, const_cast<NxgZstdDict*>(dict), err)) return false;
+    if (!c->zc_tables) {
+        std::vector<uint8_t> h(nxg_zstd_enc_tables_bytes());
+        if (!nxg_zstd_build_enc_tables(h.data())) {
+            set_err(err, "predefined zstd encoding tables");
+            return false;
+        }
+        void* t = nullptr;
+        HIPCHK(hipMalloc(&t, h.size()));
+        if (hipMemcpy(t, h.data(), h.size(), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(t);
+            set_err(err, "predefined zstd encoding tables: upload");
+            return false;
+        }
+        c->zc_tables = t;
+    }
+    if (!c->zc_ev[1]) {
+        HIPCHK(hipEventCreate(&c->zc_ev[0]));
+        HIPCHK(hipEventCreate(&c->zc_ev[1]));
+    }
+    if (!c->zc_slab) {
+        c->zc_grid = nxg_zstd_enc_grid(c->ncu);
+        HIPCHK(hipMalloc(&c->zc_slab, (size_t)c->zc_grid * nxg_zstd_enc_slab_bytes()));
+    }
+    const size_t rb = nxg_zstd_enc_rec_bytes(), sb = nxg_zstd_enc_res_bytes();
+    static_assert(sizeof(Rec) == 32 && sizeof(Res) == 16, "NxzEncRec / NxzEncRes layout");
+    if (!grow_dev(c, &c->zc_recs, &c->zc_recs_cap, (size_t)n * (rb + sb + 8 + 4) + 8, err))
+        return false;
+    if (!grow_dev(c, &c->zc_out, &c->zc_out_cap, dtotal, err)) return false;
+    uint8_t* drecs = c->zc_recs;
+    uint8_t* dres = drecs + (size_t)n * rb;
+    uint64_t* dpk = reinterpret_cast<uint64_t*>(dres + (size_t)n * sb);
+    uint32_t* dticket = reinterpret_cast<uint32_t*>(dpk + n);
+    uint32_t* dorder = dticket + 2;
+    // the order the waves draw records in: longest first
+    std::vector<uint32_t> order(n);
+    for (uint32_t i = 0; i < n; i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](uint32_t a, uint32_t b) { return rd[a].src_len > rd[b].src_len; });
+    // the batches to the device in one copy: the span of the source that holds them
+    if (lo > hi) lo = hi = 0;
+    for (uint32_t i = 0; i < n; i++)
+        if (rd[i].out_cap) rd[i].src_off -= lo;
+    const uint8_t* dsrc;
+    if (!frame_to_device(c, src + lo, hi - lo, &dsrc, err)) return false;
+    HIPCHK(hipMemcpyAsync(drecs, rd.data(), (size_t)n * rb, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(dres, 0, (size_t)n * sb, c->stream));
+    HIPCHK(hipMemsetAsync(dticket, 0, 8, c->stream));
+    HIPCHK(hipMemcpyAsync(dorder, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->zc_ev[0], c->stream));
+    HIPCHK(nxg_launch_zstd_enc(dsrc, drecs, n, dict ? dict->denc : nullptr, c->zc_tables, c->zc_out,
+                               c->zc_slab, dres, dorder, dticket, c->zc_grid, c->stream));
+    HIPCHK(hipEventRecord(c->zc_ev[1], c->stream));
+    std::vector<Res> hr(n);
+    HIPCHK(hipMemcpyAsync(hr.data(), dres, (size_t)n * sb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipEventElapsedTime(&c->zc_kernel_ms, c->zc_ev[0], c->zc_ev[1]);
+    // only the bytes written come back: the frames packed on the device, one copy, then each
+    // to its slot behind the record length and the index
+    std::vector<uint64_t> pk(n);
+    uint64_t packed = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (rd[i].out_cap && (hr[i].out_len == 0 || hr[i].out_len > rd[i].out_cap)) {
+            set_err(err, "record %u: the compressor reported %llu bytes for a slot of %llu", i,
+                    (unsigned long long)hr[i].out_len, (unsigned long long)rd[i].out_cap);
+            return false;
+        }
+        pk[i] = packed;
+        packed += hr[i].out_len;
+    }
+    if (!grow_dev(c, &c->zc_pack, &c->zc_pack_cap, packed, err)) return false;
+    if (c->zc_hpin_cap < packed) {
+        if (c->zc_hpin) HIPCHK(hipHostFree(c->zc_hpin));
+        c->zc_hpin = nullptr;
+        c->zc_hpin_cap = 0;
+        const size_t hn = std::max<size_t>(packed + packed / 4, 1 << 16);
+        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->zc_hpin), hn, hipHostMallocDefault));
+        c->zc_hpin_cap = hn;
+    }
+    uint8_t* hp = c->zc_hpin;
+    HIPCHK(hipMemcpyAsync(dpk, pk.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(nxg_launch_zstd_pack(c->zc_out, drecs, dres, dpk, n, c->zc_pack, c->ncu, c->stream));
+    HIPCHK(hipMemcpyAsync(hp, c->zc_pack, packed, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint32_t i = 0; i < n; i++) {
+        NxgArchiveRecord& r = recs[i];
+        if (r.err) continue;
+        uint8_t* o = out + r.out_off;
+        o[0] = (uint8_t)(r.len >> 24);
+        o[1] = (uint8_t)(r.len >> 16);
+        o[2] = (uint8_t)(r.len >> 8);
+        o[3] = (uint8_t)r.len;
+        memcpy(o + 4, src + r.off, ilen[i]);
+        memcpy(o + 4 + ilen[i], hp + pk[i], hr[i].out_len);
+        r.out_len = 4 + ilen[i] + hr[i].out_len;
+    }
+    return true;
+}
+
+// diagnostics, not ABI: the compressor kernel's time in the last nxg_archive_compress (ms)
+extern "C" double nxg_debug_zstd_compress_kernel_ms(NxgCtx* c) { return c ? c->zc_kernel_ms : 0.0; }
 
 // the fast archive decoder's device results (nxg_archive_fast.hip FaHead)
 struct FaHeadHost {

@@ -260,6 +260,31 @@ int nxg_zstd_grid(int ncu);
 hipError_t nxg_launch_zstd(const uint8_t* dsrc, const void* drecs, uint32_t n, const void* ddict,
                            const void* ddefs, uint8_t* dout, uint8_t* dlit, void* dres, int grid,
                            hipStream_t s);
+// zstd compression of archive records (nxg_zstd_enc.hip): the encode-side tables (built on the
+// host by the code the device runs, nxg_zstd_enc.h), the dictionary content's hash table (built on
+// the device), the compressor and the kernel that packs the frames for the copy back
+struct NxzEncDict;
+bool nxg_zstd_build_enc_dict(const uint8_t* d, uint64_t n, NxzEncDict* out);
+void nxg_zstd_enc_dict_set(NxzEncDict* d, const uint8_t* dcontent, uint32_t content_len,
+                           const uint32_t* dtable);
+bool nxg_zstd_build_enc_tables(void* o);
+uint64_t nxg_zstd_enc_dict_bytes();
+uint64_t nxg_zstd_enc_tables_bytes();
+uint64_t nxg_zstd_enc_rec_bytes();
+uint64_t nxg_zstd_enc_res_bytes();
+uint64_t nxg_zstd_enc_slab_bytes();
+uint64_t nxg_zstd_dict_table_bytes();
+uint64_t nxg_zstd_frame_bound(uint64_t len);
+int nxg_zstd_enc_grid(int ncu);
+hipError_t nxg_launch_zstd_dict_hash(const uint8_t* dcontent, uint32_t content_len, uint32_t* dtable,
+                                     hipStream_t s);
+hipError_t nxg_launch_zstd_enc(const uint8_t* dsrc, const void* drecs, uint32_t n,
+                               const void* ddict, const void* dtables, uint8_t* dout,
+                               uint8_t* dslab, void* dres, const uint32_t* dorder,
+                               uint32_t* dticket, int grid, hipStream_t s);
+hipError_t nxg_launch_zstd_pack(const uint8_t* dout, const void* drecs, const void* dres,
+                                const uint64_t* dpk, uint32_t n, uint8_t* dpacked, int ncu,
+                                hipStream_t s);
 // one share of a decoded frame's rows (nxg_share.hip): bounds (4 u64 in device memory: the first
 // child slot of a container row >= r0 / >= r1, the first control span with ctl_row >= r0 / >= r1;
 // ~0 for none), then the copy of rows [r0, r0 + nr), children [c0, c0 + nc) and control spans
