@@ -146,11 +146,23 @@ bool nxg_decode_updates(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColu
  * path selected up front runs (flags). nxg_ctx_sync completes it, runs the general fallback if
  * the homogeneous path rejected the frame, and fills the status. At most 512 async calls
  * (decode and encode together) may be in flight between syncs; the next one fails. A frame must
- * stay unchanged until nxg_ctx_sync: a fallback re-reads it there, after every later call has
- * run, and a later call of the backlog that wrote into it makes nxg_ctx_sync fail that decode
- * with an error (it never decodes the overwritten bytes). */
+ * stay unchanged until nxg_ctx_sync: a fallback (or a redo, see nxg_ctx_sync) re-reads it
+ * there, after every later call has run, and a later call of the backlog that wrote into it
+ * makes nxg_ctx_sync fail that decode with an error (it never decodes the overwritten bytes). */
 bool nxg_decode_updates_async(NxgCtx* ctx, const uint8_t* dframe, uint64_t len, NxgColumns* dout,
                               uint32_t flags, NetidxError* err);
+/* Completes every in-flight call, in order; a backlog leaves behind what its calls would have,
+ * each run to completion before the next. The status is the last decode's (or the first failing
+ * one's), the error the first failing call's. A call whose fast kernel declined is finished here,
+ * after the calls behind it have run; every later call that reads or writes memory rewritten in
+ * this way is then done again, in order, so columns and buffers may be reused within a backlog
+ * (the later call's result is the one left). Doing a call again reads its input again -- a
+ * decode its frame, an encode its columns: if a later call of the backlog wrote into that input
+ * and no earlier call's completion here has put it back, that call fails with an error naming
+ * it ("async call <index> ... keep ... unchanged until nxg_ctx_sync"), the sync returns false,
+ * and what the failed call and the calls that read its output leave behind is undefined. Whether
+ * a fast kernel declines depends on the data and on the frames and batches the ctx saw before,
+ * so only a backlog in which no call writes into what an earlier call reads is sure to complete. */
 bool nxg_ctx_sync(NxgCtx* ctx, NxgStatus* st, NetidxError* err);
 /* A connection's backlog of frames (read_task hands decode_task frame after frame over a
  * channel, channel.rs:379-443 / connection.rs:209-242): n device frames, each decoded into its own
@@ -172,7 +184,15 @@ bool nxg_encoded_len(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, uin
                      NetidxError* err);
 bool nxg_encode_updates(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, uint8_t* out,
                         uint64_t cap, uint64_t* len_out, NetidxError* err);
-/* Async device-resident variant (len_out is written at nxg_ctx_sync time). */
+/* Async device-resident variant (len_out is written at nxg_ctx_sync time). `din` (the struct and
+ * its arrays), like a decode's frame, must stay unchanged until nxg_ctx_sync: a batch the
+ * sequential-id encoder declines is encoded again there, after every later call has run, and a
+ * later call of the backlog that wrote into the columns makes nxg_ctx_sync fail that encode with
+ * an error (it never encodes the overwritten rows), unless an earlier call's completion there
+ * rewrote them first (a decode into them that fell back: the relay decode -> encode -> decode ->
+ * encode over one set of columns). `dout` may be reused by later calls of the backlog. An encode
+ * that fails (the error above, a buffer too small) may leave any bytes inside [dout, dout + cap);
+ * it writes nothing outside. */
 bool nxg_encode_updates_async(NxgCtx* ctx, const NxgColumns* din, const uint8_t* dheap,
                               uint8_t* dout, uint64_t cap, uint64_t* len_out, NetidxError* err);
 /* nxg_encode_updates plus the frame split of WriteChannel::queue_send + try_flush

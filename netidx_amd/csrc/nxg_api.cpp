@@ -665,6 +665,7 @@ bool finish_encode(NxgCtx* c, const NxgColumns* in, DevStatus* st, uint32_t slot
                               c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         h = c->hst[slot2];
+        fast = 0;  // (the tiled encoder's status from here on: last_enc_kernel reports it)
     }
     c->last_split = h.split_start;
     if (in->layout == NXG_LAYOUT_F64) c->last_enc_kernel = fast && !h.fast_fail ? 1u : 2u;
@@ -721,6 +722,16 @@ bool overlaps(const std::vector<Span>& a, const std::vector<Span>& b) {
     return false;
 }
 
+// every span of `a` lies inside one span of `by`
+bool covered(const std::vector<Span>& by, const std::vector<Span>& a) {
+    for (const Span& x : a) {
+        bool in = x.lo == x.hi;
+        for (const Span& y : by) in = in || (y.lo <= x.lo && x.hi <= y.hi);
+        if (!in) return false;
+    }
+    return true;
+}
+
 // a pending decode done again from the start, synchronously (its first attempt's columns were
 // overwritten by an earlier frame's late fallback)
 bool redo_decode(NxgCtx* c, const NxgCtx::Pending& p, NxgStatus* s, NetidxError* err) {
@@ -735,7 +746,8 @@ bool redo_decode(NxgCtx* c, const NxgCtx::Pending& p, NxgStatus* s, NetidxError*
     return finish_decode(c, p.frame, p.len, p.cols, fast, st, slot, s, err);
 }
 
-// a pending encode done again, synchronously (its input columns were rewritten after it ran)
+// a pending encode done again, synchronously (its input columns or its output buffer were
+// rewritten after it ran)
 bool redo_encode(NxgCtx* c, const NxgCtx::Pending& p, const NxgColumns* in, NetidxError* err) {
     DevStatus* st;
     uint32_t slot;
@@ -1072,11 +1084,18 @@ bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframe
 // gets its fallback and each encode its length); the status returned is the last call's, or the
 // first failing call's, and the first error is the one reported.
 //
-// A decode that falls back here rewrites its columns after every later call of the backlog has
-// run. Later calls that touched the same memory are therefore done again, in order: a decode
-// whose columns (or frame) overlap what was rewritten, and an encode whose input columns do; what
-// those rewrite joins the set. (nxg_codec.h allows a backlog to reuse columns, the later frame's
-// rows being the ones left.)
+// A call whose fast kernel declined is finished here, after every later call of the backlog has
+// run, so what it writes lands out of order. From the first such completion on, `dirty` holds the
+// memory rewritten here, and every later call that reads or writes dirty memory is done again, in
+// order: a decode whose columns or frame overlap it, an encode whose input columns or output
+// buffer do; what those rewrite joins the set. (nxg_codec.h allows a backlog to reuse columns and
+// buffers, the later call's result being the one left.)
+//
+// Doing a call again -- a fallback or a redo -- reads its input again: a decode its frame, an
+// encode its columns. If a later call of the backlog wrote into that input, the bytes the call
+// should read are gone, unless an earlier call rewrote all of it here (then it holds, the calls in
+// between having been redone in order, what the call saw). Otherwise the call fails with an error
+// naming it; it never works on the overwritten input.
 bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
     if (!c) {
         set_err(err, "null ctx");
@@ -1106,6 +1125,16 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
     if (ust) memset(ust, 0, sizeof *ust);
     bool reported = false, ok = true;
     std::vector<Span> dirty;  // memory rewritten by a call completed out of order
+    // does a call behind call i write into `rd`?
+    auto written_later = [&](size_t i, const std::vector<Span>& rd) {
+        for (size_t j = i + 1; j < ps.size(); j++) {
+            std::vector<Span> wj;
+            if (ps[j].kind == 1) cols_spans(ps[j].cols, &wj);
+            else wj.push_back(span_of(ps[j].out, ps[j].cap));
+            if (overlaps(rd, wj)) return true;
+        }
+        return false;
+    };
     for (size_t i = 0; i < ps.size(); i++) {
         auto& p = ps[i];
         c->hst[p.slot] = hs[i];
@@ -1114,32 +1143,20 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
         if (p.kind == 1) {
             std::vector<Span> w;
             cols_spans(p.cols, &w);
-            const bool stale =
-                !dirty.empty() && (overlaps(dirty, w) || overlaps(dirty, {span_of(p.frame, p.len)}));
+            const std::vector<Span> fr = {span_of(p.frame, p.len)};
+            const bool stale = !dirty.empty() && (overlaps(dirty, w) || overlaps(dirty, fr));
+            const bool reread = stale || (hs[i].fast_fail && p.fast);
             NxgStatus s;
             bool redone = false;
-            // write-after-read: a fallback re-reads the frame after every later call has run; if
-            // a later call wrote into the frame (stream-ordered reuse of the buffer as an encode
-            // output or as columns), those bytes are gone -- fail loudly instead of decoding them
-            if (!stale && hs[i].fast_fail && p.len > 0 && p.fast) {
-                const std::vector<Span> fr = {span_of(p.frame, p.len)};
-                bool clobbered = false;
-                for (size_t j = i + 1; j < ps.size() && !clobbered; j++) {
-                    std::vector<Span> wj;
-                    if (ps[j].kind == 1) cols_spans(ps[j].cols, &wj);
-                    else wj.push_back(span_of(ps[j].out, ps[j].cap));
-                    clobbered = overlaps(fr, wj);
+            if (reread && p.len > 0 && !covered(dirty, fr) && written_later(i, fr)) {
+                if (ok) {
+                    ok = false;
+                    set_err(err, "decode of async call %zu needs its frame again (%s), "
+                                 "but a later call in the backlog wrote into that frame "
+                                 "buffer; keep a frame unchanged until nxg_ctx_sync",
+                            i, stale ? "redone after an earlier call's fallback" : "fallback");
                 }
-                if (clobbered) {
-                    if (ok) {
-                        ok = false;
-                        set_err(err, "decode of async call %zu needs its frame again (fallback), "
-                                     "but a later call in the backlog wrote into that frame "
-                                     "buffer; keep a frame unchanged until nxg_ctx_sync",
-                                i);
-                    }
-                    continue;
-                }
+                continue;
             }
             if (stale) {
                 r = redo_decode(c, p, &s, &e);
@@ -1161,31 +1178,25 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
             const NxgColumns* in = p.cols ? p.cols : &dummy;
             std::vector<Span> rd;
             cols_spans(in, &rd);
-            bool clobbered = false;
-            if (p.fast && hs[i].fast_fail && (dirty.empty() || !overlaps(dirty, rd))) {
-                // write-after-read: the fallback re-reads the input columns after every later
-                // call ran; a later call that wrote into them leaves nothing to encode
-                for (size_t j = i + 1; j < ps.size() && !clobbered; j++) {
-                    std::vector<Span> wj;
-                    if (ps[j].kind == 1) cols_spans(ps[j].cols, &wj);
-                    else wj.push_back(span_of(ps[j].out, ps[j].cap));
-                    clobbered = overlaps(rd, wj);
-                }
-            }
-            if (clobbered) {
+            const Span wr = span_of(p.out, p.cap);
+            // (its output too: an earlier encode's fallback into the same buffer put that
+            // encode's frame back over this one's)
+            const bool stale = !dirty.empty() && (overlaps(dirty, rd) || overlaps(dirty, {wr}));
+            const bool reread = stale || (p.fast && hs[i].fast_fail);
+            if (reread && !covered(dirty, rd) && written_later(i, rd)) {
                 r = false;
-                set_err(&e, "encode of async call %zu needs its columns again (fallback), but a "
+                set_err(&e, "encode of async call %zu needs its columns again (%s), but a "
                             "later call in the backlog wrote into them; keep them unchanged until "
-                            "nxg_ctx_sync", i);
-            } else if (!dirty.empty() && overlaps(dirty, rd)) {
-                // its input columns were rewritten after it ran: encode again
+                            "nxg_ctx_sync", i,
+                        stale ? "redone after an earlier call's fallback" : "fallback");
+            } else if (stale) {
                 r = redo_encode(c, p, in, &e);
-                dirty.push_back(span_of(p.out, p.cap));
+                dirty.push_back(wr);
             } else {
                 bool redone = false;
                 r = finish_encode(c, in, p.st, p.slot, p.len_out, p.cap, true, &e, true, p.fast,
                                   p.heap, p.out, &redone);
-                if (redone) dirty.push_back(span_of(p.out, p.cap));
+                if (redone) dirty.push_back(wr);
             }
         }
         if (!r && ok) {
