@@ -556,6 +556,91 @@ bool nxg_archive_compress(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t* s
                           uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
                           uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err);
 
+/* ---- a window of archive records: replaces the get_batch_at loops of ArchiveReader::read_deltas
+ * (netidx-archive/src/logfile/reader.rs:590-631, up to n records per call; recorder/oneshot.rs:141
+ * asks for 1000) and ArchiveReader::build_image (reader.rs:492-557).
+ * Record i's batch is dbuf[recs[i].out_off, + recs[i].out_len); dbuf is device memory of buf_len
+ * bytes. The array nxg_archive_decompress fills feeds straight in; for an uncompressed archive the
+ * host fills out_off / out_len itself, past the RecordHeader and the index. A record with
+ * recs[i].err != 0 is skipped: its info has zero rows and err_kind 0 (the caller has recs[i].err).
+ * Bytes after a batch inside its slot are not read; slots need not be contiguous or ordered.
+ * Output: MIXED-layout device columns holding the rows of all batches back to back, in record
+ * order, then item order. id / tag / fixed / aux mean what they mean for nxg_decode_archive_batch,
+ * except that text offsets index dbuf (absolute, not the record) and that container `fixed` and
+ * child `cfixed` index out's child arrays (absolute). out->n_rows / n_children are the totals.
+ * info[i] (host memory, n entries): the record's rows [row_off, + n_rows) and children
+ * [child_off, + n_children) in `out`, consumed = its batch's length in bytes, and the status
+ * nxg_decode_archive_batch gives for the same bytes: err_kind / err_offset (relative to the
+ * record's batch start) and path -- NXG_PATH_ARCHIVE_WINDOW for a record the window's own kernels
+ * decoded, else the path of the single-batch decoder it went through.
+ * A record that fails, fails alone: its info carries (err_kind, err_offset), it has no rows
+ * (n_rows = n_children = consumed = 0), and the others decode; the reference's `?` on the first
+ * failure is the caller's decision.
+ * Routes: records shorter than opts->big_record_bytes bytes go to the window's kernels (one wave per
+ * record); those decline what the fast single-batch path declines (an Id wider than 5 bytes, Maps,
+ * Error(Value), nested or 128+-element Arrays, any parse error, a count the items do not bear
+ * out). Records of that length or more, and declined ones, go through nxg_decode_archive_batch, unchanged, into
+ * scratch columns of the ctx and are copied to their place. big_record_bytes 0 (or opts NULL) is
+ * the default, NXG_ARCHIVE_WINDOW_BIG_DEFAULT; 1 sends every record through the single-batch
+ * decoder; UINT64_MAX every record that is not declined through the window's kernels. The result
+ * does not depend on the route.
+ * Capacity: when out->cap_rows or out->cap_children is too small the call returns false with
+ * *need_rows / *need_children set to the exact totals (they are written on success too). A-priori
+ * bounds: rows <= sum(out_len) / 2, children <= sum(out_len).
+ * Misuse (false): a null argument, columns that are not device MIXED columns, a record outside
+ * buf_len, an async operation pending on the ctx. Synchronous. */
+#define NXG_PATH_ARCHIVE_WINDOW 7
+#define NXG_ARCHIVE_WINDOW_BIG_DEFAULT 131072
+typedef struct NxgArchiveBatchInfo { /* one per record, written by the call */
+    uint64_t row_off, n_rows;        /* the record's rows in `out`, record order then item order */
+    uint64_t child_off, n_children;
+    uint64_t consumed;               /* the batch's length in bytes */
+    int32_t err_kind;                /* as nxg_decode_archive_batch's status */
+    uint32_t path;                   /* which decoder */
+    uint64_t err_offset;             /* relative to the record's batch start */
+} NxgArchiveBatchInfo;
+typedef struct NxgArchiveWindowOpts {
+    uint64_t big_record_bytes; /* 0 = default */
+} NxgArchiveWindowOpts;
+bool nxg_archive_decode_window(NxgCtx* ctx, const uint8_t* dbuf, uint64_t buf_len,
+                               const NxgArchiveRecord* recs, uint32_t n,
+                               const NxgArchiveWindowOpts* opts /* NULL = defaults */,
+                               NxgColumns* out, NxgArchiveBatchInfo* info, uint64_t* need_rows,
+                               uint64_t* need_children, NetidxError* err);
+
+/* The image of a decoded window: replaces the image.extend(...) fold of build_image
+ * (reader.rs:519-552), a HashMap::extend in record order, then item order. For each Id the value
+ * of its last row in `window` (the columns nxg_archive_decode_window wrote). Event::Unsubscribed
+ * is a value like any other: it stays in the image as tag NXG_TAG_UNSUBSCRIBED. With `keep`
+ * (n_ids bytes of device memory; NULL = every Id) rows whose Id has keep[id] == 0 are dropped, as
+ * the reference's filter drops them (reader.rs:519-525, 546-552); n_filtered counts those rows.
+ * Archive Ids come from a counter (writer.rs:314-315) and the reader knows max_id
+ * (reader.rs:226-237): n_ids = max_id + 1. An Id >= n_ids is a false return whose message names
+ * the Id and the row; a well-formed archive has none.
+ * Output: the caller's device arrays of cap_rows entries each (cap_rows >= min(n_ids, the window's
+ * rows) always suffices; fewer is a false return): id, tag, fixed, aux of each winner and src_row,
+ * its row in the window, in ascending Id order (the reference's map has no order; this one is
+ * deterministic). n_rows and n_filtered are written by the call.
+ * The image borrows the window: children and text stay where the window decode put them. An
+ * NxgColumns made of the image's row arrays (n_rows, cap_rows) and the window's child arrays
+ * (n_children, cap_children) is accepted as it is by nxg_encode_archive_batch(..., heap = dbuf,
+ * ...) -- the encoder reaches children only through `fixed` -- and its bytes are the image record
+ * the writer stores. Chaining over windows needs no further call: encode the image and make it
+ * record 0 of the next window. Synchronous; false on misuse (null arguments, non-device columns, an
+ * async operation pending) or a HIP failure. */
+typedef struct NxgArchiveImage {
+    uint64_t cap_rows; /* >= min(n_ids, window rows) */
+    uint64_t* id;      /* device arrays of cap_rows entries */
+    uint8_t* tag;
+    uint64_t* fixed;
+    uint32_t* aux;
+    uint64_t* src_row;           /* the winning row's index in the window columns */
+    uint64_t n_rows, n_filtered; /* written by the call */
+} NxgArchiveImage;
+bool nxg_archive_build_image(NxgCtx* ctx, const NxgColumns* window, uint64_t n_ids,
+                             const uint8_t* keep /* [n_ids] device, NULL = every Id */,
+                             NxgArchiveImage* out, NetidxError* err);
+
 /* ---- the publisher <-> subscriber connection (BASELINE configs[0]) ------------------------
  * Replaces hello_publisher (netidx/src/subscriber/connection.rs:120-140), ClientCtx::hello
  * (publisher/server.rs:367-381), read_task / flush_buf (channel.rs:107-126, 379-443) and the

@@ -13,7 +13,8 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     frame_parse_header, frame_split, lib, Comm, NxgRange, range_link, Session,
                     msg_subscribe, msg_subscribed, msg_heartbeat, msg_parse, msg_update,
                     TAG_UNSUBSCRIBED, Resolver, ResolverClient, TagView, TAG_BINS, WriteCols,
-                    NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES)
+                    NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES, ArchiveImage,
+                    WindowCapacity)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
            "frame_split", "frame_header", "frame_parse_header", "LAYOUT_F64", "LAYOUT_MIXED",
@@ -23,4 +24,4 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "Comm", "NxgRange", "range_link", "Session", "msg_subscribe", "msg_subscribed",
            "msg_heartbeat", "msg_parse", "msg_update", "TAG_UNSUBSCRIBED", "Resolver",
            "ResolverClient", "TagView", "TAG_BINS", "WriteCols", "NxgWriteCols", "WRITE_REPLY",
-           "WRITE_NO_WID", "PATH_WRITES"]
+           "WRITE_NO_WID", "PATH_WRITES", "ArchiveImage", "WindowCapacity"]

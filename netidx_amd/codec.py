@@ -139,6 +139,28 @@ class NxgArchiveRecord(C.Structure):
                 ("out_len", C.c_uint64), ("err", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class NxgArchiveBatchInfo(C.Structure):
+    _fields_ = [("row_off", C.c_uint64), ("n_rows", C.c_uint64), ("child_off", C.c_uint64),
+                ("n_children", C.c_uint64), ("consumed", C.c_uint64), ("err_kind", C.c_int32),
+                ("path", C.c_uint32), ("err_offset", C.c_uint64)]
+
+    FIELDS = ("row_off", "n_rows", "child_off", "n_children", "consumed", "err_kind", "path",
+              "err_offset")
+
+    def dict(self):
+        return {k: int(getattr(self, k)) for k in self.FIELDS}
+
+
+class NxgArchiveWindowOpts(C.Structure):
+    _fields_ = [("big_record_bytes", C.c_uint64)]
+
+
+class NxgArchiveImage(C.Structure):
+    _fields_ = [("cap_rows", C.c_uint64), ("id", C.c_void_p), ("tag", C.c_void_p),
+                ("fixed", C.c_void_p), ("aux", C.c_void_p), ("src_row", C.c_void_p),
+                ("n_rows", C.c_uint64), ("n_filtered", C.c_uint64)]
+
+
 class NxgStatus(C.Structure):
     _fields_ = [
         ("n_rows", C.c_uint64), ("n_children", C.c_uint64), ("n_ctl", C.c_uint64),
@@ -235,6 +257,16 @@ SIGNATURES = {
     "nxg_encode_archive_batch": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
                                             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                             C.POINTER(NetidxError)]),
+    "nxg_archive_decode_window": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.POINTER(NxgArchiveRecord), C.c_uint32,
+                                             C.POINTER(NxgArchiveWindowOpts),
+                                             C.POINTER(NxgColumns),
+                                             C.POINTER(NxgArchiveBatchInfo),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                             C.POINTER(NetidxError)]),
+    "nxg_archive_build_image": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_uint64,
+                                           C.c_void_p, C.POINTER(NxgArchiveImage),
+                                           C.POINTER(NetidxError)]),
     "nxg_session_connect": (C.c_void_p, [C.c_char_p, C.c_uint16, C.POINTER(NetidxError)]),
     "nxg_session_listen": (C.c_void_p, [C.c_char_p, C.c_uint16, C.POINTER(C.c_uint16),
                                         C.POINTER(NetidxError)]),
@@ -414,6 +446,68 @@ class Columns:
         return out
 
 
+class WindowCapacity(CodecError):
+    """nxg_archive_decode_window: the columns are too small; need_rows / need_children are the
+    exact totals."""
+
+    def __init__(self, msg, need_rows, need_children):
+        super().__init__(msg)
+        self.need_rows, self.need_children = need_rows, need_children
+
+
+class ArchiveImage:
+    """The image of a decoded window (nxg_archive_build_image): id / tag / fixed / aux / src_row
+    tensors of n_rows winners in ascending Id order, n_filtered rows dropped by `keep`. It
+    borrows the window: children and text stay where the window decode put them."""
+
+    def __init__(self, cap, device):
+        import torch
+        n = max(cap, 1)
+        self.id = torch.zeros(n, dtype=torch.int64, device=device)
+        self.tag = torch.zeros(n, dtype=torch.uint8, device=device)
+        self.fixed = torch.zeros(n, dtype=torch.int64, device=device)
+        self.aux = torch.zeros(n, dtype=torch.int32, device=device)
+        self.src_row = torch.zeros(n, dtype=torch.int64, device=device)
+        torch.cuda.synchronize(device)  # (as Columns: the zero fill is done)
+        self.s = NxgArchiveImage()
+        self.s.cap_rows = n
+        for k in ("id", "tag", "fixed", "aux", "src_row"):
+            setattr(self.s, k, getattr(self, k).data_ptr())
+
+    @property
+    def n_rows(self):
+        return self.s.n_rows
+
+    @property
+    def n_filtered(self):
+        return self.s.n_filtered
+
+    def numpy(self):
+        n = self.s.n_rows
+        return {"id": self.id[:n].cpu().numpy().view(np.uint64), "tag": self.tag[:n].cpu().numpy(),
+                "fixed": self.fixed[:n].cpu().numpy().view(np.uint64),
+                "aux": self.aux[:n].cpu().numpy().view(np.uint32),
+                "src_row": self.src_row[:n].cpu().numpy().view(np.uint64)}
+
+    def columns(self, window_cols):
+        """The image as columns for encode_archive(view, heap=the window's buffer): the image's
+        row arrays with the window's child arrays (a view; both must stay alive)."""
+        v = _ColumnsView()
+        v.keep = (self, window_cols)
+        v.id, v.tag, v.fixed, v.aux = self.id, self.tag, self.fixed, self.aux
+        v.s = NxgColumns()
+        C.memmove(C.byref(v.s), C.byref(window_cols.s), C.sizeof(NxgColumns))
+        v.s.cap_rows, v.s.n_rows = self.s.cap_rows, self.s.n_rows
+        v.s.n_ctl = 0
+        for k in ("id", "tag", "fixed", "aux"):
+            setattr(v.s, k, getattr(self, k).data_ptr())
+        return v
+
+
+class _ColumnsView:
+    pass
+
+
 class WriteCols:
     """The two further fields of To::Write rows (NxgWriteCols): wflags (WRITE_REPLY |
     WRITE_NO_WID) and wid (the WriteId) per row. torch tensors on `device` (pinned host memory
@@ -557,6 +651,40 @@ class Codec:
                                             n, indexed, C.c_void_p(out.data_ptr()), out.numel(),
                                             C.byref(need), C.byref(err)), err)
         return out, [(recs[i].out_off, recs[i].out_len, recs[i].err) for i in range(n)]
+
+    def archive_decode_window(self, buf, recs, cols, big_record_bytes=0):
+        """A window of archive records decoded in one call (nxg_archive_decode_window). buf: the
+        device uint8 tensor holding the batches; recs: [(out_off, out_len)] or [(out_off, out_len,
+        err)] (archive_decompress's list feeds straight in); cols: MIXED device Columns. Returns
+        the per-record infos (NxgArchiveBatchInfo). Raises WindowCapacity when cols is too
+        small."""
+        n = len(recs)
+        r = (NxgArchiveRecord * max(n, 1))()
+        for i, t in enumerate(recs):
+            r[i].out_off, r[i].out_len = t[0], t[1]
+            r[i].err = t[2] if len(t) > 2 else 0
+        info = (NxgArchiveBatchInfo * max(n, 1))()
+        opts = NxgArchiveWindowOpts(big_record_bytes)
+        nr, nc, err = C.c_uint64(0), C.c_uint64(0), NetidxError()
+        ok = lib().nxg_archive_decode_window(self.ctx, C.c_void_p(buf.data_ptr()), buf.numel(), r,
+                                             n, C.byref(opts), C.byref(cols.s), info,
+                                             C.byref(nr), C.byref(nc), C.byref(err))
+        if not ok and (nr.value > cols.s.cap_rows or nc.value > cols.s.cap_children):
+            msg = err.msg.decode() if err.msg else "capacity"
+            lib().nxg_error_free(C.byref(err))
+            raise WindowCapacity(msg, nr.value, nc.value)
+        _check(ok, err)
+        return [info[i] for i in range(n)]
+
+    def archive_build_image(self, cols, n_ids, keep=None):
+        """The image of a decoded window (nxg_archive_build_image): the last row per Id, rows
+        whose Id has keep[id] == 0 dropped (keep: a device uint8 tensor of n_ids entries, or
+        None). Returns an ArchiveImage; .columns(cols) is the view encode_archive takes."""
+        img = ArchiveImage(min(n_ids, cols.s.n_rows), cols.id.device)
+        err = NetidxError()
+        _check(lib().nxg_archive_build_image(self.ctx, C.byref(cols.s), n_ids, _ptr(keep),
+                                             C.byref(img.s), C.byref(err)), err)
+        return img
 
     def archive_compress(self, src, records, indexed=False, zdict=None):
         """Uncompressed archive records (host bytes `src`, [(off, len)] after each RecordHeader)

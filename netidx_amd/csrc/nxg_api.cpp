@@ -155,6 +155,12 @@ struct NxgCtx {
     float zc_kernel_ms = 0.f;
     DevStatus last{};  // last completed decode's device status (diagnostics)
     uint64_t fa_last[8] = {};  // the last fast archive attempt's FaHead (diagnostics)
+    // a window of archive records / its image (nxg_archive_window.hip): the head and the records
+    // or the image's table, and the pinned host mirror of head + records
+    uint8_t* aw_dev = nullptr;
+    size_t aw_dev_cap = 0;
+    uint8_t* aw_host = nullptr;
+    size_t aw_host_cap = 0;
     uint64_t last_split = 0;  // last completed encode's DevStatus.split_start
 };
 
@@ -882,6 +888,8 @@ void nxg_ctx_destroy(NxgCtx* c) {
     for (hipEvent_t e : c->zc_ev)
         if (e) (void)hipEventDestroy(e);
     if (c->dheap) (void)hipFree(c->dheap);
+    if (c->aw_dev) (void)hipFree(c->aw_dev);
+    if (c->aw_host) (void)hipHostFree(c->aw_host);
     if (c->dwflags) (void)hipFree(c->dwflags);
     if (c->dwid) (void)hipFree(c->dwid);
     if (c->dst) (void)hipFree(c->dst);
@@ -1927,6 +1935,246 @@ bool nxg_decode_archive_batch(NxgCtx* c, const uint8_t* buf, uint64_t len, NxgCo
     out->layout = NXG_LAYOUT_MIXED;
     if (ust) *ust = s;
     if (consumed) *consumed = r.consumed;
+    return true;
+}
+
+// ---- a window of archive records and its image (nxg_archive_window.hip) -----------------------
+namespace {
+bool ensure_aw(NxgCtx* c, size_t dev_bytes, size_t host_bytes, NetidxError* err) {
+    if (dev_bytes > c->aw_dev_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->aw_dev) HIPCHK(hipFree(c->aw_dev));
+        c->aw_dev = nullptr;
+        const size_t sz = std::max(dev_bytes, c->aw_dev_cap * 2);
+        c->aw_dev_cap = 0;
+        HIPCHK(hipMalloc(&c->aw_dev, sz));
+        c->aw_dev_cap = sz;
+    }
+    if (host_bytes > c->aw_host_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->aw_host) HIPCHK(hipHostFree(c->aw_host));
+        c->aw_host = nullptr;
+        const size_t sz = std::max(host_bytes, c->aw_host_cap * 2);
+        c->aw_host_cap = 0;
+        HIPCHK(hipHostMalloc(&c->aw_host, sz, hipHostMallocDefault));
+        c->aw_host_cap = sz;
+    }
+    return true;
+}
+
+// the ctx's scratch columns for one record of `len` bytes on the single-batch decoder (rows <=
+// len / 2, children <= len)
+bool ensure_aw_cols(NxgCtx* c, uint64_t len, NetidxError* err) {
+    const uint64_t cr = len / 2 + 1, cc = len + 1;
+    if (c->dcols_valid && c->dcols.layout == NXG_LAYOUT_MIXED && c->dcols.cap_rows >= cr &&
+        c->dcols.cap_children >= cc)
+        return true;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t ck = c->dcols_valid ? std::max<uint64_t>(c->dcols.cap_ctl, 1) : 1;
+    if (c->dcols_valid) cols_free_impl(&c->dcols);
+    c->dcols_valid = false;
+    if (!cols_alloc_impl(NXG_LAYOUT_MIXED, cr, cc, ck, NXG_MEM_DEVICE, &c->dcols, err)) return false;
+    c->dcols_valid = true;
+    return true;
+}
+}  // namespace
+
+bool nxg_archive_decode_window(NxgCtx* c, const uint8_t* dbuf, uint64_t buf_len,
+                               const NxgArchiveRecord* recs, uint32_t n,
+                               const NxgArchiveWindowOpts* opts, NxgColumns* out,
+                               NxgArchiveBatchInfo* info, uint64_t* need_rows,
+                               uint64_t* need_children, NetidxError* err) {
+    // (the arguments first, the ctx after them: misuse is reported before any device work)
+    if (!out || !need_rows || !need_children || (n && (!recs || !info)) || (!dbuf && buf_len)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (out->mem != NXG_MEM_DEVICE || !mixed_capable(out) || !out->id || !out->fixed) {
+        set_err(err, "a window of archive records decodes into device MIXED-layout columns");
+        return false;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        if (recs[i].err) continue;
+        if (recs[i].out_off > buf_len || recs[i].out_len > buf_len - recs[i].out_off) {
+            set_err(err, "record %u (offset %llu, %llu bytes) lies outside the buffer of %llu bytes",
+                    i, (unsigned long long)recs[i].out_off, (unsigned long long)recs[i].out_len,
+                    (unsigned long long)buf_len);
+            return false;
+        }
+        if (recs[i].out_len >= (1ull << 40)) {
+            set_err(err, "record %u too large (%llu bytes)", i, (unsigned long long)recs[i].out_len);
+            return false;
+        }
+    }
+    if (!c) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    if (buf_len && !is_device_ptr(dbuf)) {
+        set_err(err, "the window's buffer must be device memory");
+        return false;
+    }
+    uint64_t big = opts && opts->big_record_bytes ? opts->big_record_bytes
+                                                  : (uint64_t)NXG_ARCHIVE_WINDOW_BIG_DEFAULT;
+    big = std::min<uint64_t>(big, 0x7fffffffull);  // the wave kernels use 32-bit record offsets
+    *need_rows = *need_children = 0;
+    out->n_rows = out->n_children = out->n_ctl = out->n_heartbeat = 0;
+    out->layout = NXG_LAYOUT_MIXED;
+    if (n == 0) return true;
+    const size_t bytes = sizeof(AwHead) + (size_t)n * sizeof(AwRec);
+    if (!ensure_aw(c, bytes, bytes, err)) return false;
+    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host);
+    AwRec* hr = reinterpret_cast<AwRec*>(c->aw_host + sizeof(AwHead));
+    uint8_t* dhead = c->aw_dev;
+    uint8_t* drecs = c->aw_dev + sizeof(AwHead);
+    uint32_t n_wave = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        AwRec r{};
+        r.off = recs[i].out_off;
+        r.len = recs[i].out_len;
+        r.route = recs[i].err ? 0u : (r.len < big ? 1u : 2u);
+        n_wave += r.route == 1u;
+        hr[i] = r;
+    }
+    memset(hh, 0, sizeof *hh);
+    HIPCHK(hipMemcpyAsync(c->aw_dev, c->aw_host, bytes, hipMemcpyHostToDevice, c->stream));
+    if (n_wave) {
+        HIPCHK(nxg_launch_aw_count(dbuf, drecs, n, c->ncu, c->stream));
+        HIPCHK(hipMemcpyAsync(hr, drecs, (size_t)n * sizeof(AwRec), hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    // the records of the single-batch decoder, in order: each into the scratch columns, then to
+    // its place by the host's running sums (the device scan below gives the same offsets)
+    uint64_t rows_run = 0, kids_run = 0;
+    uint32_t n_emit = 0;
+    bool patched = false;
+    for (uint32_t i = 0; i < n; i++) {
+        NxgArchiveBatchInfo f{};
+        AwRec& r = hr[i];
+        if (r.route == 1u && !r.declined) {
+            f.path = NXG_PATH_ARCHIVE_WINDOW;
+            n_emit++;
+        } else if (r.route != 0u) {
+            if (!ensure_aw_cols(c, r.len, err)) return false;
+            NxgColumns sc = c->dcols;
+            NxgStatus st{};
+            uint64_t used = 0;
+            if (!nxg_decode_archive_batch(c, dbuf + r.off, r.len, &sc, &st, &used, err))
+                return false;
+            f.err_kind = st.err_kind;
+            f.err_offset = st.err_offset;
+            f.path = st.path;
+            r.rows = st.err_kind ? 0 : st.n_rows;
+            r.kids = st.err_kind ? 0 : st.n_children;
+            r.consumed = st.err_kind ? 0 : used;
+            r.route = 2u;
+            r.declined = 0u;
+            patched = true;
+            if (rows_run + r.rows <= out->cap_rows && kids_run + r.kids <= out->cap_children)
+                HIPCHK(nxg_launch_aw_rebase(desc_of(&sc), desc_of(out), r.rows, r.kids, rows_run,
+                                            kids_run, r.off, c->stream));
+        }
+        f.row_off = rows_run;
+        f.n_rows = r.rows;
+        f.child_off = kids_run;
+        f.n_children = r.kids;
+        f.consumed = r.consumed;
+        info[i] = f;
+        rows_run += r.rows;
+        kids_run += r.kids;
+    }
+    *need_rows = rows_run;
+    *need_children = kids_run;
+    if (rows_run > out->cap_rows || kids_run > out->cap_children) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        set_err(err, "the window needs %llu rows and %llu children; the columns hold %llu and %llu",
+                (unsigned long long)rows_run, (unsigned long long)kids_run,
+                (unsigned long long)out->cap_rows, (unsigned long long)out->cap_children);
+        return false;
+    }
+    if (n_emit) {
+        if (patched)
+            HIPCHK(hipMemcpyAsync(drecs, hr, (size_t)n * sizeof(AwRec), hipMemcpyHostToDevice,
+                                  c->stream));
+        HIPCHK(nxg_launch_aw_scan(drecs, n, dhead, c->stream));
+        HIPCHK(nxg_launch_aw_emit(dbuf, drecs, n, desc_of(out), dhead, c->ncu, c->stream));
+        HIPCHK(hipMemcpyAsync(c->aw_host, c->aw_dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_emit) {
+        bool same = hh->rows == rows_run && hh->kids == kids_run && !hh->emit_fail;
+        for (uint32_t i = 0; same && i < n; i++)
+            same = hr[i].row_off == info[i].row_off && hr[i].child_off == info[i].child_off;
+        if (!same) {
+            set_err(err, "internal error: the window's emit pass disagrees with its count pass");
+            return false;
+        }
+    }
+    out->n_rows = rows_run;
+    out->n_children = kids_run;
+    return true;
+}
+
+bool nxg_archive_build_image(NxgCtx* c, const NxgColumns* window, uint64_t n_ids,
+                             const uint8_t* keep, NxgArchiveImage* out, NetidxError* err) {
+    if (!window || !out) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (window->mem != NXG_MEM_DEVICE || window->layout != NXG_LAYOUT_MIXED || !window->id ||
+        !window->tag || !window->fixed || !window->aux) {
+        set_err(err, "the image is built from device MIXED-layout columns");
+        return false;
+    }
+    const uint64_t rows = window->n_rows;
+    if (out->cap_rows < std::min(n_ids, rows)) {
+        set_err(err, "the image's capacity is %llu rows; min(n_ids, window rows) = %llu",
+                (unsigned long long)out->cap_rows, (unsigned long long)std::min(n_ids, rows));
+        return false;
+    }
+    if (out->cap_rows && (!out->id || !out->tag || !out->fixed || !out->aux || !out->src_row)) {
+        set_err(err, "null output array");
+        return false;
+    }
+    if (!c) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    if ((rows && !is_device_ptr(window->id)) || (out->cap_rows && !is_device_ptr(out->id)) ||
+        (keep && !is_device_ptr(keep))) {
+        set_err(err, "the image needs device columns, device outputs and a device keep array");
+        return false;
+    }
+    out->n_rows = out->n_filtered = 0;
+    if (!ensure_aw(c, sizeof(AwHead) + nxg_aw_image_scratch_bytes(n_ids), sizeof(AwHead), err))
+        return false;
+    HIPCHK(nxg_launch_aw_image(desc_of(window), rows, n_ids, keep, c->aw_dev + sizeof(AwHead),
+                               out->cap_rows, out->id, out->tag, out->fixed, out->aux,
+                               out->src_row, c->aw_dev, c->stream));
+    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host);
+    HIPCHK(hipMemcpyAsync(hh, c->aw_dev, sizeof(AwHead), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (n_ids == 0 && rows) hh->bad_row = 0;  // every Id is past an empty table
+    if (hh->bad_row != ~0ull) {
+        uint64_t v = 0;
+        HIPCHK(hipMemcpy(&v, window->id + hh->bad_row, 8, hipMemcpyDeviceToHost));
+        set_err(err, "Id %llu at row %llu is not below n_ids = %llu", (unsigned long long)v,
+                (unsigned long long)hh->bad_row, (unsigned long long)n_ids);
+        return false;
+    }
+    out->n_rows = hh->n_image;
+    out->n_filtered = hh->n_filtered;
     return true;
 }
 

@@ -244,6 +244,40 @@ hipError_t nxg_launch_dec_fa(const uint8_t* buf, uint64_t W, uint32_t p0, uint64
                              hipStream_t s);
 hipError_t nxg_arch_decode(const uint8_t* buf, uint64_t W, const ColsDesc& cols, uint8_t* scratch,
                            uint32_t* cap_flag, int max_rounds, NxgArchResult* res, hipStream_t s);
+// a window of archive records and its image (nxg_archive_window.hip)
+// one record of the window (uploaded by the host, counted and placed on the device)
+struct AwRec {
+    uint64_t off, len;             // the batch in dbuf
+    uint64_t rows, kids;           // count pass (wave route), or the host (decoder route)
+    uint64_t consumed;
+    uint64_t row_off, child_off;   // scan
+    uint32_t route;                // 0 skipped, 1 the wave kernels, 2 the single-batch decoder
+    uint32_t declined;             // count pass: the record goes to the single-batch decoder
+};
+static_assert(sizeof(AwRec) == 64, "AwRec layout");
+struct AwHead {
+    uint64_t rows, kids;     // scan: totals
+    uint32_t emit_fail;      // emit: a record the count pass took did not decode again (a bug)
+    uint32_t pad;
+    uint64_t n_image;        // image: rows gathered
+    uint64_t n_filtered;     // image: rows dropped by `keep`
+    uint64_t bad_row;        // image: the first row whose Id is >= n_ids (~0: none)
+    uint64_t pad2[2];
+};
+static_assert(sizeof(AwHead) == 64, "AwHead layout");
+hipError_t nxg_launch_aw_count(const uint8_t* dbuf, void* drecs, uint32_t n, int ncu,
+                               hipStream_t s);
+hipError_t nxg_launch_aw_scan(void* drecs, uint32_t n, void* dhead, hipStream_t s);
+hipError_t nxg_launch_aw_emit(const uint8_t* dbuf, const void* drecs, uint32_t n,
+                              const ColsDesc& cols, void* dhead, int ncu, hipStream_t s);
+hipError_t nxg_launch_aw_rebase(const ColsDesc& src, const ColsDesc& dst, uint64_t nr, uint64_t nc,
+                                uint64_t row_off, uint64_t child_off, uint64_t text_off,
+                                hipStream_t s);
+uint64_t nxg_aw_image_scratch_bytes(uint64_t n_ids);
+hipError_t nxg_launch_aw_image(const ColsDesc& win, uint64_t n_rows, uint64_t n_ids,
+                               const uint8_t* keep, uint8_t* scratch, uint64_t cap, uint64_t* oid,
+                               uint8_t* otag, uint64_t* ofixed, uint32_t* oaux, uint64_t* osrc,
+                               void* dhead, hipStream_t s);
 // zstd decompression of compressed archive records (nxg_zstd.hip): host-side table builders and
 // the launch; the device structures are opaque here (their sizes from the *_bytes functions)
 struct NxzDictDev;
