@@ -526,7 +526,10 @@ NXG_DEV uint32_t block_compressed(ZLds& L, Frame& f, const uint8_t* ip, uint32_t
         if (off == 0 || off > f.op + hist) return Z_CORRUPT;
         emit_match(L, f, ml, off, lane);
     }
-    if (b.bp > 0) return Z_CORRUPT;  // bits left over (libzstd: < BIT_DStream_completed)
+    // the stream ends with the last sequence: no bits left over, and none read below its start
+    // (those read as 0: a truncated stream would decode to sequences nobody wrote; libzstd
+    // refuses it at the next reload, BIT_DStream_overflow)
+    if (b.bp != 0) return Z_CORRUPT;
     const uint32_t rest = l.total - l.pos;
     if (f.op + rest > f.cap) return Z_DST_SMALL;
     emit_lits(L, f, l, rest, lane);
