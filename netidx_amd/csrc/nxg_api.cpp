@@ -57,7 +57,15 @@ struct NxgCtx {
     // status ring: one DevStatus per call, the whole ring re-zeroed once per lap
     DevStatus* dst = nullptr;
     DevStatus* hst = nullptr;  // pinned mirror
+    DevStatus* hst_dev = nullptr;  // ... as the device addresses it (the status gather's target)
     uint32_t calls = 0;
+    // Calls numbered below gathered_to (call sequence numbers: `calls` at their begin_call,
+    // compared modulo 2^32) have a status gather enqueued behind them (nxg_status.hip), so
+    // nxg_ctx_sync gathers only the pending calls from there on. At most kStatusRing/2 calls are
+    // pending and a gather covers pending calls only, so it never overwrites an hst slot the
+    // host has not consumed: the host took its copy of every older slot at the sync before.
+    // Every error return of a function that enqueues gathers clears the record (gather_forget).
+    uint32_t gathered_to = 0;
     uint32_t epoch = 0;
     uint64_t* tstat = nullptr;
     size_t tstat_words = 0;
@@ -130,6 +138,7 @@ struct NxgCtx {
         uint32_t flags = 0;            // decode: the caller's NXG_DECODE_* flags
         const uint8_t* heap = nullptr;  // encode: the heap and the output buffer
         uint8_t* out = nullptr;
+        uint32_t seq = 0;  // the call's sequence number (NxgCtx::calls at its begin_call)
     };
     std::vector<Pending> pending;
     // zstd (compressed archive records): predefined tables, literal buffers, descriptors
@@ -197,6 +206,28 @@ bool end_call(NxgCtx* c, NetidxError* err) {
     nxg_zero_used = true;
     HIPCHK(hipMemsetAsync(nxg_zero_slot, 0, sizeof(DevStatus), c->stream));
     return true;
+}
+
+// Enqueues a status gather for the pending calls that none covers yet (the pending calls used
+// consecutive ring slots and sequence numbers). Nothing to do: no launch.
+bool gather_pending(NxgCtx* c, NetidxError* err) {
+    if (c->pending.empty()) return true;
+    const uint32_t first = c->pending.front().seq;
+    const uint32_t span = c->pending.back().seq - first + 1;  // (modulo 2^32, like `done`)
+    uint32_t done = c->gathered_to - first;  // leading calls already covered
+    if (done > span) done = 0;               // the record is older than this backlog
+    if (done == span) return true;
+    HIPCHK(nxg_launch_status_gather(c->dst, c->hst_dev, (first + done) % kStatusRing,
+                                    std::min<uint32_t>(span - done, kStatusRing), kStatusRing,
+                                    c->stream));
+    c->gathered_to = first + span;
+    return true;
+}
+
+// After a failure: whatever gather was enqueued may cover calls that never became pending, or
+// may not have been launched at all; the next nxg_ctx_sync gathers every pending call again.
+void gather_forget(NxgCtx* c) {
+    c->gathered_to = c->pending.empty() ? c->calls : c->pending.front().seq;
 }
 
 bool ensure_tstat(NxgCtx* c, size_t words, NetidxError* err) {
@@ -839,6 +870,8 @@ NxgCtx* nxg_ctx_new(int device, NetidxError* err) {
     if ((e = hipHostMalloc(&c->hst, sizeof(DevStatus) * (kStatusRing + 1), hipHostMallocDefault)) !=
         hipSuccess)
         return fail("hipHostMalloc(status)", e);
+    if ((e = hipHostGetDevicePointer((void**)&c->hst_dev, c->hst, 0)) != hipSuccess)
+        return fail("hipHostGetDevicePointer(status)", e);
     // general decode: run summaries + bases (no initialisation needed)
     const size_t gw = (size_t)gdec2::MAX_RUNS * (gdec2::RUN_WORDS + 4);
     if ((e = hipMalloc(&c->gruns, gw * 8)) != hipSuccess) return fail("hipMalloc(gruns)", e);
@@ -1011,22 +1044,24 @@ bool nxg_decode_updates_async(NxgCtx* c, const uint8_t* dframe, uint64_t len, Nx
     DevStatus* st;
     uint32_t slot;
     if (!begin_call(c, &st, &slot, err)) return false;
+    const uint32_t seq = c->calls - 1;
     int fast = FAST_NONE;
     const bool ok = !(flags & NXG_DECODE_HINT_MIXED)
                         ? enqueue_dec_fast(c, dframe, len, dout, st, &fast, err)
                         : enqueue_dec_mixed(c, dframe, len, dout, st, &fast, err);
     if (!end_call(c, err) || !ok) return false;
     c->pending.push_back({1, fast, dframe, len, dout, nullptr, 0, st, slot, flags});
+    c->pending.back().seq = seq;
     return true;
 }
 
-bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframes,
-                             const uint64_t* lens, NxgColumns* const* douts, uint32_t flags,
-                             NetidxError* err) {
-    if (!c || (n && (!dframes || !lens || !douts))) {
-        set_err(err, "null argument");
-        return false;
-    }
+}  // extern "C"
+
+namespace {
+
+bool decode_frames_async_impl(NxgCtx* c, uint32_t n, const uint8_t* const* dframes,
+                              const uint64_t* lens, NxgColumns* const* douts, uint32_t flags,
+                              NetidxError* err) {
     if (c->pending.size() + n > kStatusRing / 2) {
         set_err(err, "too many in-flight async calls (max %d); call nxg_ctx_sync", kStatusRing / 2);
         return false;
@@ -1049,7 +1084,7 @@ bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframe
         for (uint32_t j = 0; j < n; j++)
             if (!nxg_decode_updates_async(c, dframes[j], lens[j], douts[j], flags, err))
                 return false;
-        return true;
+        return gather_pending(c, err);
     }
     if (!set_device(c, err)) return false;
     // two descriptor arrays: frame j's probe runs beside frame j - 1's emit
@@ -1078,6 +1113,7 @@ bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframe
         // an empty frame launches nothing: its zero-ahead slot is cleared here
         if (lens[j] == 0) HIPCHK(hipMemsetAsync(f.zst, 0, sizeof(DevStatus), c->stream));
         pend.push_back({1, FAST_RUN, dframes[j], lens[j], douts[j], nullptr, 0, st, slot});
+        pend.back().seq = c->calls - 1;
     }
     // (the frames become pending only once their launches are enqueued: a failed launch leaves
     // no call behind whose status slot no kernel wrote)
@@ -1085,7 +1121,25 @@ bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframe
     // (these frames skipped the sequential-id decoder: they count toward its skip)
     c->seq_left = c->seq_left > n ? c->seq_left - n : 0;
     c->pending.insert(c->pending.end(), pend.begin(), pend.end());
-    return true;
+    return gather_pending(c, err);
+}
+
+}  // namespace
+
+extern "C" {
+
+// The backlog's status gather is enqueued right behind its last launch (gather_pending), so the
+// statuses are in host memory the moment the last decode ends and nxg_ctx_sync waits once.
+bool nxg_decode_frames_async(NxgCtx* c, uint32_t n, const uint8_t* const* dframes,
+                             const uint64_t* lens, NxgColumns* const* douts, uint32_t flags,
+                             NetidxError* err) {
+    if (!c || (n && (!dframes || !lens || !douts))) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (decode_frames_async_impl(c, n, dframes, lens, douts, flags, err)) return true;
+    gather_forget(c);
+    return false;
 }
 
 // Completes every in-flight call in order (every one, even after a failure, so that each decode
@@ -1110,26 +1164,24 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
         return false;
     }
     if (!set_device(c, err)) return false;
+    // One wait: the status slots of the pending calls reach c->hst by a gather kernel in stream
+    // order (nxg_status.hip), enqueued behind a backlog by nxg_decode_frames_async already and
+    // here for the calls made since; the end of that kernel publishes them to the host.
+    const bool gathered = gather_pending(c, err);
     std::vector<NxgCtx::Pending> ps;
     ps.swap(c->pending);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    // the in-flight calls used consecutive ring slots: at most two copies cover them
-    std::vector<DevStatus> hs(ps.size());
-    if (!ps.empty()) {
-        const uint32_t s0 = ps.front().slot, s1 = ps.back().slot;
-        if (s0 <= s1) {
-            HIPCHK(hipMemcpyAsync(c->hst + s0, c->dst + s0, sizeof(DevStatus) * (s1 - s0 + 1),
-                                  hipMemcpyDeviceToHost, c->stream));
-        } else {
-            HIPCHK(hipMemcpyAsync(c->hst + s0, c->dst + s0, sizeof(DevStatus) * (kStatusRing - s0),
-                                  hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(c->hst, c->dst, sizeof(DevStatus) * (s1 + 1),
-                                  hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        // (kept aside: the fallbacks below take ring slots of their own, which may wrap)
-        for (size_t i = 0; i < ps.size(); i++) hs[i] = c->hst[ps[i].slot];
+    if (!gathered) {
+        // (the calls are dropped, as after any failed step of this function; the stream is
+        // drained so that nothing of them is still running when the caller goes on)
+        (void)hipStreamSynchronize(c->stream);
+        c->gathered_to = c->calls;
+        return false;
     }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->gathered_to = c->calls;  // nothing is pending: the record starts afresh
+    // (kept aside: the fallbacks below take ring slots of their own, which may wrap)
+    std::vector<DevStatus> hs(ps.size());
+    for (size_t i = 0; i < ps.size(); i++) hs[i] = c->hst[ps[i].slot];
     if (ust) memset(ust, 0, sizeof *ust);
     bool reported = false, ok = true;
     std::vector<Span> dirty;  // memory rewritten by a call completed out of order
@@ -1149,13 +1201,20 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
         NetidxError e{nullptr};
         bool r;
         if (p.kind == 1) {
-            std::vector<Span> w;
-            cols_spans(p.cols, &w);
-            const std::vector<Span> fr = {span_of(p.frame, p.len)};
-            const bool stale = !dirty.empty() && (overlaps(dirty, w) || overlaps(dirty, fr));
-            const bool reread = stale || (hs[i].fast_fail && p.fast);
             NxgStatus s;
             bool redone = false;
+            // The common case: nothing was rewritten out of order so far and this call's kernel
+            // did not decline, so the call is neither stale nor read again, and no fallback can
+            // rewrite its columns (every one of finish_decode's needs fast_fail): its spans are
+            // not needed.
+            const bool plain = dirty.empty() && !hs[i].fast_fail;
+            std::vector<Span> w, fr;
+            if (!plain) {
+                cols_spans(p.cols, &w);
+                fr.push_back(span_of(p.frame, p.len));
+            }
+            const bool stale = !dirty.empty() && (overlaps(dirty, w) || overlaps(dirty, fr));
+            const bool reread = stale || (hs[i].fast_fail && p.fast);
             if (reread && p.len > 0 && !covered(dirty, fr) && written_later(i, fr)) {
                 if (ok) {
                     ok = false;
@@ -1173,7 +1232,10 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
                 r = finish_decode(c, p.frame, p.len, p.cols, p.fast, p.st, p.slot, &s, &e, true,
                                   &redone);
             }
-            if (redone) dirty.insert(dirty.end(), w.begin(), w.end());
+            if (redone) {
+                if (plain) cols_spans(p.cols, &w);
+                dirty.insert(dirty.end(), w.begin(), w.end());
+            }
             if (r) {
                 p.cols->layout =
                     (!mixed_capable(p.cols) || s.path == 1) ? NXG_LAYOUT_F64 : NXG_LAYOUT_MIXED;
@@ -2628,11 +2690,12 @@ bool nxg_encode_updates_async(NxgCtx* c, const NxgColumns* din, const uint8_t* d
     DevStatus* st;
     uint32_t slot;
     if (!begin_call(c, &st, &slot, err)) return false;
+    const uint32_t seq = c->calls - 1;
     int fast = 0;
     const bool ok = enqueue_encode(c, din, dheap, dout, cap, st, err, &fast);
     if (!end_call(c, err) || !ok) return false;
     c->pending.push_back({2, fast, nullptr, 0, const_cast<NxgColumns*>(din), len_out, cap, st,
-                          slot, 0, dheap, dout});
+                          slot, 0, dheap, dout, seq});
     return true;
 }
 

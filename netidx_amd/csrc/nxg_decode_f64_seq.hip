@@ -12,7 +12,9 @@
 //   - wave g decodes records [256 g, 256 g + 256): lane j takes records j, j + 64, ... four at a
 //     time, one 16-byte load each (the record's second block is lane j + 1's first, by DPP), and
 //     checks every record completely: length byte, variant 4, id varint width, value tag 9, AND
-//     id == i0 + k; then 64 consecutive rows per column store.
+//     id == i0 + k; then 64 consecutive rows per column store. A wave whose ids all have one
+//     varint width (every wave but at most four) makes the same check as one masked equality
+//     with the header its record must have, and decodes nothing (emit_full_pairs_uniform).
 //
 // Why that is the reference's decode exactly: record 0 starts at byte 0; if record k at pos(k) is a
 // valid Update of length L_k then the sequential decoder's next message starts at
@@ -175,6 +177,9 @@ NXG_DEV bool emit_full(const uint8_t* __restrict__ wire, uint64_t W, uint64_t p0
 #ifndef NXG_F64S_PAIR
 #define NXG_F64S_PAIR 1  // 1: a lane decodes two consecutive records, one 16-byte store per column
 #endif
+#ifndef NXG_F64S_UNIFORM
+#define NXG_F64S_UNIFORM 1  // (with PAIR) waves of one id width: header by equality (A/B: 0)
+#endif
 // A whole wave in pairs: lane j of batch r takes records k = 2 (64 r + j) and k + 1 (rows k0 + k,
 // even: one 16-byte aligned store per column). The two records lie in the 48 bytes from the
 // aligned block of the first: blocks A and B are loaded, C is the next lane's A or B (DPP; its
@@ -264,6 +269,99 @@ NXG_DEV bool emit_full_pairs(const uint8_t* __restrict__ wire, uint64_t W, uint6
     return bad;
 }
 
+// emit_full_pairs for a whole wave whose ids all have the same varint width (no width change
+// inside it: every wave of a frame but at most four). L, the id width nb = L - 11 and the value
+// offset L - 8 are then scalars, record k lies at s0 + k L, and the one header a record may have
+// is known before it is read: L, 04, the canonical varint of ib + k, 09. That header is built
+// from the id and compared with the record's first 3 + nb bytes in one masked 64-bit equality
+// (f64rec16::seq_head_const: why this accepts exactly what rec_check16 and the id comparison
+// accept), and the id column receives ib + k itself: no varint is decoded, no per-lane length
+// is selected. Loads, block sharing, extract16 and stores are emit_full_pairs's.
+template <int R>
+NXG_DEV bool emit_full_pairs_uniform(const uint8_t* __restrict__ wire, uint64_t p0, uint32_t L,
+                                     uint64_t k0, uint64_t i0, uint64_t* __restrict__ oid,
+                                     uint64_t* __restrict__ oval, uint64_t cap, uint32_t lane,
+                                     bool& over) {
+    using namespace f64rec16;
+    constexpr int RP = R / 2;
+    const uint64_t a0 = p0 & ~15ull;
+    const uint8_t* __restrict__ base = wire + a0;
+    const uint32_t s0 = (uint32_t)(p0 & 15u);
+    const uint32_t nb = L - 11u;
+    const uint64_t hc = seq_head_const(nb), hm = seq_head_mask(nb);
+    const uint32_t c0 = (uint32_t)hc, c1 = (uint32_t)(hc >> 32);
+    const uint32_t m0 = (uint32_t)hm, m1 = (uint32_t)(hm >> 32);
+    uint4 A[RP], B[RP], Cq[RP];
+    uint32_t oa[RP];
+#pragma unroll
+    for (int r = 0; r < RP; r++) {
+        const uint32_t k = 2 * (r * 64 + lane);
+        oa[r] = s0 + k * L;
+        const uint32_t ab = oa[r] & ~15u;
+        A[r] = ld16s(base + ab);
+        B[r] = ld16s(base + ab + 16);
+        if (lane == 63) Cq[r] = ld16s(base + ab + 32);
+    }
+    uint32_t bad = 0;
+    const uint64_t ib = i0 + k0;
+#pragma unroll
+    for (int r = 0; r < RP; r++) {
+        const uint32_t k = 2 * (r * 64 + lane);
+        const uint32_t ab = oa[r] & ~15u;
+        const uint32_t nA[4] = {wave_next(A[r].x), wave_next(A[r].y), wave_next(A[r].z),
+                                wave_next(A[r].w)};
+        const uint32_t nB[4] = {wave_next(B[r].x), wave_next(B[r].y), wave_next(B[r].z),
+                                wave_next(B[r].w)};
+        const bool at32 = ((oa[r] + 2 * L) & ~15u) == ab + 32;
+        uint32_t C[4];
+        C[0] = at32 ? nA[0] : nB[0];
+        C[1] = at32 ? nA[1] : nB[1];
+        C[2] = at32 ? nA[2] : nB[2];
+        C[3] = at32 ? nA[3] : nB[3];
+        if (lane == 63) C[0] = Cq[r].x, C[1] = Cq[r].y, C[2] = Cq[r].z, C[3] = Cq[r].w;
+        const uint64_t ida = ib + k, idb = ida + 1;
+        uint32_t h0, h1;
+        const uint32_t d[8] = {A[r].x, A[r].y, A[r].z, A[r].w, B[r].x, B[r].y, B[r].z, B[r].w};
+        uint32_t e0, e1, e2, e3;
+        extract16(d, oa[r] & 15u, e0, e1, e2, e3);
+        seq_head_id(ida, h0, h1);
+        bad |= ((e0 ^ (h0 | c0)) & m0) | ((e1 ^ (h1 | c1)) & m1);
+        const uint64_t va = rec_value16(e1, e2, e3, L);
+        const uint32_t sb = (oa[r] & 15u) + L;  // 12..31
+        const bool up = sb >= 16;
+        const uint32_t d2[8] = {up ? B[r].x : A[r].x, up ? B[r].y : A[r].y, up ? B[r].z : A[r].z,
+                                up ? B[r].w : A[r].w, up ? C[0] : B[r].x, up ? C[1] : B[r].y,
+                                up ? C[2] : B[r].z, up ? C[3] : B[r].w};
+        extract16(d2, sb & 15u, e0, e1, e2, e3);
+        seq_head_id(idb, h0, h1);
+        bad |= ((e0 ^ (h0 | c0)) & m0) | ((e1 ^ (h1 | c1)) & m1);
+        const uint64_t vb = rec_value16(e1, e2, e3, L);
+        const uint64_t row = k0 + k;
+        if (row + 1 < cap) {
+            const uint4 iv = make_uint4((uint32_t)ida, (uint32_t)(ida >> 32), (uint32_t)idb,
+                                        (uint32_t)(idb >> 32));
+            const uint4 vv = make_uint4((uint32_t)va, (uint32_t)(va >> 32), (uint32_t)vb,
+                                        (uint32_t)(vb >> 32));
+            if (NXG_F64S_NT & 1) {
+                __builtin_nontemporal_store(*reinterpret_cast<const v4u*>(&iv),
+                                            reinterpret_cast<v4u*>(oid + row));
+                __builtin_nontemporal_store(*reinterpret_cast<const v4u*>(&vv),
+                                            reinterpret_cast<v4u*>(oval + row));
+            } else {
+                *reinterpret_cast<uint4*>(oid + row) = iv;
+                *reinterpret_cast<uint4*>(oval + row) = vv;
+            }
+        } else {
+            if (row < cap) {
+                oid[row] = ida;
+                oval[row] = va;
+            }
+            over = true;
+        }
+    }
+    return bad != 0;
+}
+
 }  // namespace f64s
 
 // One wave per WREC records; the grid covers the most records W bytes can hold (W / 12), and the
@@ -332,8 +430,13 @@ __global__ __launch_bounds__(f64s::TPB) void nxg_f64s_kernel(const uint8_t* __re
     const uint64_t pend = p0 + (uint64_t)ks * L + (uint64_t)(WREC - ks) * (L + 1);  // pos(k0 + WREC)
     bool over = false, bad = b > 5;
     if (!bad && pend + 48 <= W) {
-        bad = NXG_F64S_PAIR ? emit_full_pairs<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over)
-                            : emit_full<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over);
+        // (ks == WREC: one id width in the whole wave -- all but at most four waves of a frame)
+        if (NXG_F64S_PAIR && NXG_F64S_UNIFORM && ks == WREC)
+            bad = emit_full_pairs_uniform<R>(wire, p0, L, k0, i0, oid, oval, cap, lane, over);
+        else
+            bad = NXG_F64S_PAIR
+                      ? emit_full_pairs<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over)
+                      : emit_full<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over);
     } else if (!bad) {
         // near the frame's end: n = #{k < WREC : pos(k0 + k) < W} (pos increases by 12..16 per
         // record); the frame's last record must end exactly at W

@@ -90,6 +90,40 @@ NXG_DEV void rec_decode16(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, ui
     val = ((uint64_t)bswap32(lo) << 32) | bswap32(hi);  // big-endian f64 (pack.rs:592-598)
 }
 
+// The header of a record whose id is known: where the id to expect has nb = L - 11 varint bytes,
+// i.e. lies in [2^(7(nb-1)), 2^(7nb)) (nb = 1: [0, 2^7)), the only first 3 + nb bytes that
+// rec_check16 and an id comparison accept together are
+//     L, 04, the canonical varint of the id, 09
+// -- rec_check16 wants byte 0 = L, byte 1 = 04, the continuation bit on exactly the first nb - 1
+// id bytes and 09 behind them; the comparison wants the 7-bit groups of those nb bytes to spell
+// the id; for an id of that range these nb bytes are its canonical varint, and no other bytes
+// pass both. (rec_check16's `rem >= L` is the caller's: the record lies inside the frame.) So the
+// check is one masked 64-bit equality against a word built from the id, and nothing is decoded.
+//
+// seq_head_const: every byte of that word but the id's 7-bit groups (wave-uniform callers keep it
+// and the mask in scalar registers); seq_head_mask: its first 3 + nb bytes.
+NXG_DEV uint64_t seq_head_const(uint32_t nb) {
+    const uint64_t cont = 0x8080808080ull & ((1ull << (8u * (nb - 1u))) - 1ull);
+    return (uint64_t)(11u + nb) | (4ull << 8) | (cont << 16) | (9ull << (8u * (2u + nb)));
+}
+NXG_DEV uint64_t seq_head_mask(uint32_t nb) { return ~0ull >> (8u * (5u - nb)); }
+// the 7-bit groups of id (< 2^35) spread into bytes 2..6 of the header word (lo, hi halves)
+NXG_DEV void seq_head_id(uint64_t id, uint32_t& h0, uint32_t& h1) {
+    const uint32_t lo = (uint32_t)id, hi = (uint32_t)(id >> 32);
+    const uint32_t v = (lo & 0x7fu) | ((lo << 1) & 0x7f00u) | ((lo << 2) & 0x7f0000u) |
+                       ((lo << 3) & 0x7f000000u);      // groups 0..3: header bytes 2..5
+    const uint32_t g4 = (lo >> 28) | ((hi & 7u) << 4);  // group 4: header byte 6
+    h0 = v << 16;
+    h1 = (v >> 16) | (g4 << 16);
+}
+// the f64 bits of a record of length L (value at byte L - 8 of e0..e3)
+NXG_DEV uint64_t rec_value16(uint32_t e1, uint32_t e2, uint32_t e3, uint32_t L) {
+    const uint32_t o = L - 8u;  // 4..8
+    const uint32_t lo = o >= 8u ? e2 : alignbyte(e2, e1, o & 3u);
+    const uint32_t hi = o >= 8u ? e3 : alignbyte(e3, e2, o & 3u);
+    return ((uint64_t)bswap32(lo) << 32) | bswap32(hi);  // big-endian f64 (pack.rs:592-598)
+}
+
 // SWAR: 0x80 in each byte of x whose value is in [12, 16] (record lengths)
 NXG_DEV uint32_t len_bytes(uint32_t x) {
     const uint32_t y = x & 0x7f7f7f7fu;

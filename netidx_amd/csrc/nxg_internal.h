@@ -98,6 +98,10 @@ inline DevStatus* nxg_take_zero_slot() {
     nxg_zero_used = true;
     return nxg_zero_slot;
 }
+// status gather (nxg_status.hip): ring slots s0, s0 + 1, ... (n of them, modulo `ring`) copied to
+// the pinned host mirror, whose device address is `hst_dev`, in stream order
+hipError_t nxg_launch_status_gather(const DevStatus* dst, DevStatus* hst_dev, uint32_t s0,
+                                    uint32_t n, uint32_t ring, hipStream_t s);
 // f64 decode of any f64 frame in one pass (nxg_decode_f64_x.hip): `tstat` holds
 // nxg_dec_f64x_groups(W) epoch-tagged words (no initialisation needed).
 uint64_t nxg_dec_f64x_groups(uint64_t W);
