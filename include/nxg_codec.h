@@ -555,6 +555,27 @@ bool nxg_archive_decompress(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t*
 bool nxg_archive_compress(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t* src,
                           uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
                           uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err);
+/* nxg_archive_compress with options (NULL: the defaults, which is nxg_archive_compress itself).
+ * literals: how a block's literals may be Huffman-coded.
+ *   NXG_ZSTD_LIT_DICT_TREE (0): with the dictionary's tree only (Treeless_Literals_Block); frames
+ *     without a zstd-format dictionary have raw literals.
+ *   NXG_ZSTD_LIT_BLOCK_TREES (1): a block may also build a tree from its own literals (code
+ *     lengths of at most 11 bits) and describe it (Compressed_Literals_Block; direct or
+ *     FSE-compressed weights), when that section is smaller than raw, RLE and the treeless form
+ *     with the tree the frame's reader has at that block -- the dictionary's, or the last one a
+ *     block of the frame described. No dictionary is needed for Huffman-coded literals.
+ * Slots, record layout, errors and determinism are those of nxg_archive_compress; a frame of one
+ * block, and every frame without a zstd-format dictionary, is never larger than with literals
+ * 0. An unknown `literals` value or a non-zero `reserved` word fails the call. */
+enum { NXG_ZSTD_LIT_DICT_TREE = 0, NXG_ZSTD_LIT_BLOCK_TREES = 1 };
+typedef struct NxgZstdCompressOpts {
+    uint32_t literals;
+    uint32_t reserved[3];
+} NxgZstdCompressOpts;
+bool nxg_archive_compress_opts(NxgCtx* ctx, const NxgZstdDict* dict, const uint8_t* src,
+                               uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
+                               const NxgZstdCompressOpts* opts /* NULL = defaults */,
+                               uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err);
 
 /* ---- a window of archive records: replaces the get_batch_at loops of ArchiveReader::read_deltas
  * (netidx-archive/src/logfile/reader.rs:590-631, up to n records per call; recorder/oneshot.rs:141

@@ -155,6 +155,13 @@ class NxgArchiveWindowOpts(C.Structure):
     _fields_ = [("big_record_bytes", C.c_uint64)]
 
 
+class NxgZstdCompressOpts(C.Structure):
+    _fields_ = [("literals", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+ZSTD_LIT_DICT_TREE, ZSTD_LIT_BLOCK_TREES = 0, 1
+
+
 class NxgArchiveImage(C.Structure):
     _fields_ = [("cap_rows", C.c_uint64), ("id", C.c_void_p), ("tag", C.c_void_p),
                 ("fixed", C.c_void_p), ("aux", C.c_void_p), ("src_row", C.c_void_p),
@@ -251,6 +258,11 @@ SIGNATURES = {
                                         C.POINTER(NxgArchiveRecord), C.c_uint32, C.c_bool,
                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                         C.POINTER(NetidxError)]),
+    "nxg_archive_compress_opts": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.POINTER(NxgArchiveRecord), C.c_uint32, C.c_bool,
+                                             C.POINTER(NxgZstdCompressOpts), C.c_void_p,
+                                             C.c_uint64, C.POINTER(C.c_uint64),
+                                             C.POINTER(NetidxError)]),
     "nxg_decode_archive_batch": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.POINTER(NxgColumns), C.POINTER(NxgStatus),
                                             C.POINTER(C.c_uint64), C.POINTER(NetidxError)]),
@@ -686,11 +698,13 @@ class Codec:
                                              C.byref(img.s), C.byref(err)), err)
         return img
 
-    def archive_compress(self, src, records, indexed=False, zdict=None):
+    def archive_compress(self, src, records, indexed=False, zdict=None, literals=0):
         """Uncompressed archive records (host bytes `src`, [(off, len)] after each RecordHeader)
-        compressed on the device (nxg_archive_compress). Returns (host uint8 array,
+        compressed on the device (nxg_archive_compress_opts). Returns (host uint8 array,
         [(out_off, out_len, err)]): record i's compressed record -- u32 BE length | index | zstd
-        frame -- is out[out_off:out_off + out_len]."""
+        frame -- is out[out_off:out_off + out_len]. literals: ZSTD_LIT_DICT_TREE (0, Huffman
+        literals with the dictionary's tree only) or ZSTD_LIT_BLOCK_TREES (1, a block may build and
+        describe its own tree)."""
         b = src if isinstance(src, np.ndarray) else np.frombuffer(bytes(src), np.uint8)
         b = np.ascontiguousarray(b)
         n = len(records)
@@ -699,12 +713,14 @@ class Codec:
             recs[i].off, recs[i].len = o, ln
         need, err = C.c_uint64(0), NetidxError()
         dh = zdict.h if zdict else None
-        _check(lib().nxg_archive_compress(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs,
-                                          n, indexed, None, 0, C.byref(need), C.byref(err)), err)
+        opts = NxgZstdCompressOpts(literals=literals)
+        f = lib().nxg_archive_compress_opts
+        _check(f(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs, n, indexed,
+                 C.byref(opts), None, 0, C.byref(need), C.byref(err)), err)
         out = np.zeros(max(need.value, 1), np.uint8)
-        _check(lib().nxg_archive_compress(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs,
-                                          n, indexed, C.c_void_p(out.ctypes.data), need.value,
-                                          C.byref(need), C.byref(err)), err)
+        _check(f(self.ctx, dh, C.c_void_p(b.ctypes.data), len(b), recs, n, indexed,
+                 C.byref(opts), C.c_void_p(out.ctypes.data), need.value, C.byref(need),
+                 C.byref(err)), err)
         return out, [(recs[i].out_off, recs[i].out_len, recs[i].err) for i in range(n)]
 
     def decode_batch(self, frame, layout=LAYOUT_MIXED, flags=0, device="cuda"):

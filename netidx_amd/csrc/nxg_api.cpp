@@ -1694,8 +1694,25 @@ static bool grow_dev(NxgCtx* c, uint8_t** p, size_t* cap, size_t need, NetidxErr
 bool nxg_archive_compress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* src,
                           uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
                           uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err) {
+    return nxg_archive_compress_opts(c, dict, src, src_len, recs, n, indexed, nullptr, out, cap,
+                                     need, err);
+}
+
+bool nxg_archive_compress_opts(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* src,
+                               uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
+                               const NxgZstdCompressOpts* opts, uint8_t* out, uint64_t cap,
+                               uint64_t* need, NetidxError* err) {
     if (!c || (n && (!recs || !src))) {
         set_err(err, "null argument");
+        return false;
+    }
+    const uint32_t literals = opts ? opts->literals : (uint32_t)NXG_ZSTD_LIT_DICT_TREE;
+    if (literals > NXG_ZSTD_LIT_BLOCK_TREES) {
+        set_err(err, "NxgZstdCompressOpts.literals: unknown value %u", literals);
+        return false;
+    }
+    if (opts && (opts->reserved[0] | opts->reserved[1] | opts->reserved[2])) {
+        set_err(err, "NxgZstdCompressOpts.reserved must be zero");
         return false;
     }
     if (!c->pending.empty()) {
@@ -1818,7 +1835,8 @@ bool nxg_archive_compress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* src
     HIPCHK(hipMemcpyAsync(dorder, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->zc_ev[0], c->stream));
     HIPCHK(nxg_launch_zstd_enc(dsrc, drecs, n, dict ? dict->denc : nullptr, c->zc_tables, c->zc_out,
-                               c->zc_slab, dres, dorder, dticket, c->zc_grid, c->stream));
+                               c->zc_slab, dres, dorder, dticket, c->zc_grid, literals,
+                               c->stream));
     HIPCHK(hipEventRecord(c->zc_ev[1], c->stream));
     std::vector<Res> hr(n);
     HIPCHK(hipMemcpyAsync(hr.data(), dres, (size_t)n * sb, hipMemcpyDeviceToHost, c->stream));

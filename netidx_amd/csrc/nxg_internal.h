@@ -319,7 +319,7 @@ hipError_t nxg_launch_zstd_dict_hash(const uint8_t* dcontent, uint32_t content_l
 hipError_t nxg_launch_zstd_enc(const uint8_t* dsrc, const void* drecs, uint32_t n,
                                const void* ddict, const void* dtables, uint8_t* dout,
                                uint8_t* dslab, void* dres, const uint32_t* dorder,
-                               uint32_t* dticket, int grid, hipStream_t s);
+                               uint32_t* dticket, int grid, uint32_t literals, hipStream_t s);
 hipError_t nxg_launch_zstd_pack(const uint8_t* dout, const void* drecs, const void* dres,
                                 const uint64_t* dpk, uint32_t n, uint8_t* dpacked, int ncu,
                                 hipStream_t s);

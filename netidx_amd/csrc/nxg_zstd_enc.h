@@ -12,6 +12,8 @@
 //   the sequences section, predefined distributions                     3.1.1.3.2 (ZSTD_encodeSequences)
 //   Huffman codes from weights, 1 / 4 streams                           4.2 (HUF_compress1X / 4X)
 //   literals section headers                                            3.1.1.3.1
+//   a block's own Huffman tree: length-limited code lengths, the tree's   4.2.1 (HUF_buildCTable,
+//   description as direct or FSE-compressed weights                      HUF_writeCTable)
 // Functions are pure (no memory outside their arguments). Loads of bytes the caller produced
 // itself go through a `Ld` functor: the device reads its own per-wave buffers with loads that
 // bypass the CU's L1, the host with plain loads.
@@ -128,9 +130,10 @@ struct HufCode {
     uint8_t nbits;  // 0: the symbol has no code
     uint8_t pad;
 };
-NXZ_HD void build_huf_enc(HufCode* codes, const uint8_t* w, uint32_t n_sym, uint32_t max_bits) {
-    uint32_t start[kHufMaxBits + 2] = {0};
-    uint32_t cnt[kHufMaxBits + 2] = {0};
+// `start`, `cnt`: kHufMaxBits + 2 words of scratch each
+NXZ_HD void build_huf_enc_ws(HufCode* codes, const uint8_t* w, uint32_t n_sym, uint32_t max_bits,
+                             uint32_t* start, uint32_t* cnt) {
+    for (uint32_t k = 0; k < kHufMaxBits + 2; k++) start[k] = cnt[k] = 0;
     for (uint32_t s = 0; s < n_sym; s++) cnt[w[s]]++;
     uint32_t acc = 0;
     for (uint32_t k = 1; k <= max_bits; k++) {
@@ -146,6 +149,10 @@ NXZ_HD void build_huf_enc(HufCode* codes, const uint8_t* w, uint32_t n_sym, uint
         codes[s] = HufCode{(uint16_t)(start[k] >> (k - 1)), (uint8_t)(max_bits + 1 - k), 0};
         start[k] += 1u << (k - 1);
     }
+}
+NXZ_HD void build_huf_enc(HufCode* codes, const uint8_t* w, uint32_t n_sym, uint32_t max_bits) {
+    uint32_t start[kHufMaxBits + 2], cnt[kHufMaxBits + 2];
+    build_huf_enc_ws(codes, w, n_sym, max_bits, start, cnt);
 }
 
 // ---- the backward bitstream, written forwards (BIT_CStream_t) -----------------------------------
@@ -349,6 +356,297 @@ NXZ_HD uint32_t write_lit_header(uint8_t* dst, const LitPlan& p, uint32_t n, uin
         dst[p.hdr + 2 * k + 1] = (uint8_t)(p.ssz[k] >> 8);
     }
     return p.hdr + 6;
+}
+
+// ---- a block's own Huffman tree (Compressed_Literals_Block) ----------------------------------------
+// From a block's literal histogram: code lengths of at most kHufEncBits, the codes
+// (build_huf_enc), and the tree's description (direct 4-bit weights or FSE-compressed weights,
+// the smaller). Integer arithmetic only, ties broken by symbol value: the tree is a function of
+// the histogram alone.
+constexpr uint32_t kHufEncBits = 11;    // the longest code written (readers accept kHufMaxBits)
+constexpr uint32_t kHufDescMax = 128;   // header byte + at most 127 bytes of FSE-compressed weights
+// Below this many literals no tree pays for itself: the section is at least 3 (header) + 2 (the
+// smallest description: one listed weight) + n / 8 + 1 (a bit per literal and the marker) bytes
+// against 1 + n raw, smaller only from n = 6.
+constexpr uint32_t kFreshMinLits = 6;
+enum : uint32_t { kLitDictTree = 0, kLitBlockTrees = 1 };  // NxgZstdCompressOpts.literals
+
+// 2 KiB of working memory (the device lays it over its literal stage, idle at that time).
+// a: the symbols' (count << 8 | symbol) keys sorted, then their counts, then their code lengths,
+// in place; afterwards build_huf_enc_ws' scratch. hist: the counts by symbol, dead once sorted;
+// its bytes then hold the symbols in sorted order, the description and the weights' FSE tables.
+struct HufWork {
+    uint32_t a[256];
+    union {
+        uint32_t hist[256];
+        struct {
+            uint8_t ord[256];
+            uint8_t desc[kHufDescMax + 4];
+            uint16_t fstate[64];
+            FseSym ftt[13];
+            int16_t norm[14];
+            uint16_t cumul[16];
+            uint8_t tsym[64];
+            uint32_t cnt[16];
+        } t;
+    };
+};
+static_assert(sizeof(HufWork) == 2048, "laid over the literal stage");
+
+// hist -> the present symbols sorted by (count, symbol) ascending: counts in a[0, n), symbols in
+// t.ord[0, n). Returns n. Serial (the device sorts with the whole wave: the keys are distinct, so
+// every sort gives this order).
+NXZ_HD uint32_t huf_sort_hist(HufWork& W) {
+    uint32_t n = 0;
+    for (uint32_t s = 0; s < 256; s++) {
+        const uint32_t c = W.hist[s];
+        if (!c) continue;
+        const uint32_t key = (c << 8) | s;
+        uint32_t i = n++;
+        for (; i > 0 && W.a[i - 1] > key; i--) W.a[i] = W.a[i - 1];
+        W.a[i] = key;
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        W.t.ord[i] = (uint8_t)W.a[i];
+        W.a[i] >>= 8;
+    }
+    return n;
+}
+
+// The weights of n >= 2 sorted symbols (huf_sort_hist): minimum-redundancy code lengths computed
+// in place (Moffat and Katajainen 1995: parents left to right, internal depths right to left, leaf
+// depths right to left), lengths above kHufEncBits cut to it and the Kraft sum repaired on the
+// lengths' counts (one code of the limit and one of the deepest shorter length become two one bit
+// longer: the sum falls by one unit of 2^-limit per step, so it ends at exactly 1), the lengths
+// then dealt longest first to the symbols in sorted order. w[256]: weight = max_bits + 1 - length,
+// 0 for an absent symbol; *n_sym: the last present symbol + 1.
+NXZ_HD void huf_build_weights(HufWork& W, uint32_t n, uint8_t* w, uint32_t* n_sym,
+                              uint32_t* max_bits) {
+    uint32_t* A = W.a;
+    const int32_t N = (int32_t)n;
+    A[0] += A[1];
+    int32_t root = 0, leaf = 2, next;
+    for (next = 1; next < N - 1; next++) {
+        if (leaf >= N || A[root] < A[leaf]) {
+            A[next] = A[root];
+            A[root++] = (uint32_t)next;
+        } else {
+            A[next] = A[leaf++];
+        }
+        if (leaf >= N || (root < next && A[root] < A[leaf])) {
+            A[next] += A[root];
+            A[root++] = (uint32_t)next;
+        } else {
+            A[next] += A[leaf++];
+        }
+    }
+    A[N - 2] = 0;
+    for (next = N - 3; next >= 0; next--) A[next] = A[A[next]] + 1;
+    int32_t avbl = 1, used = 0;
+    uint32_t dpth = 0;
+    root = N - 2;
+    next = N - 1;
+    while (avbl > 0) {
+        while (root >= 0 && A[root] == dpth) {
+            used++;
+            root--;
+        }
+        while (avbl > used) {
+            A[next--] = dpth;
+            avbl--;
+        }
+        avbl = 2 * used;
+        dpth++;
+        used = 0;
+    }
+    uint32_t* nc = W.t.cnt;
+    for (uint32_t l = 0; l <= kHufEncBits; l++) nc[l] = 0;
+    for (uint32_t i = 0; i < n; i++) nc[A[i] > kHufEncBits ? kHufEncBits : A[i]]++;
+    uint32_t total = 0;
+    for (uint32_t l = 1; l <= kHufEncBits; l++) total += nc[l] << (kHufEncBits - l);
+    while (total > (1u << kHufEncBits)) {
+        nc[kHufEncBits]--;
+        for (uint32_t l = kHufEncBits - 1; l > 0; l--)
+            if (nc[l]) {
+                nc[l]--;
+                nc[l + 1] += 2;
+                break;
+            }
+        total--;
+    }
+    uint32_t mb = kHufEncBits;
+    while (!nc[mb]) mb--;
+    for (uint32_t s = 0; s < 256; s++) w[s] = 0;
+    uint32_t i = 0, last = 0;
+    for (uint32_t l = mb; l > 0; l--)
+        for (uint32_t k = nc[l]; k > 0; k--) {
+            const uint32_t s = W.t.ord[i++];
+            w[s] = (uint8_t)(mb + 1 - l);
+            last = s > last ? s : last;
+        }
+    *n_sym = last + 1;
+    *max_bits = mb;
+}
+
+// The listed weights w[0, listed) FSE-compressed at W.t.desc + 1 (HUF_compressWeights): their
+// histogram normalised to an accuracy log of 5 (below 64 weights) or 6, the NCount header
+// (FSE_writeNCount), two interleaved states from the last weight back. Returns the bytes (0: not
+// representable -- one weight value only, or 128 bytes and more).
+NXZ_HD uint32_t huf_fse_weights(HufWork& W, const uint8_t* w, uint32_t listed) {
+    uint32_t* cnt = W.t.cnt;
+    int16_t* norm = W.t.norm;
+    for (uint32_t s = 0; s < 14; s++) cnt[s] = 0;
+    for (uint32_t i = 0; i < listed; i++) cnt[w[i]]++;
+    uint32_t max_sym = 0, distinct = 0, big = 0;
+    for (uint32_t s = 0; s <= kHufEncBits; s++) {
+        if (!cnt[s]) continue;
+        max_sym = s;
+        distinct++;
+        if (cnt[s] > cnt[big]) big = s;
+    }
+    if (distinct < 2) return 0;
+    const uint32_t al = listed < 64 ? 5u : 6u, size = 1u << al;
+    // every present weight at least 1; what is left goes to the most frequent, what is too much
+    // comes off the largest
+    uint32_t sum = 0;
+    for (uint32_t s = 0; s <= max_sym; s++) {
+        uint32_t p = cnt[s] * size / listed;
+        if (cnt[s] && !p) p = 1;
+        norm[s] = (int16_t)p;
+        sum += p;
+    }
+    if (sum < size) norm[big] = (int16_t)(norm[big] + (size - sum));
+    for (; sum > size; sum--) {
+        uint32_t m = 0;
+        for (uint32_t s = 1; s <= max_sym; s++)
+            if (norm[s] > norm[m]) m = s;
+        norm[m]--;
+    }
+    uint8_t* d = W.t.desc + 1;
+    BitW hw(d, kHufDescMax - 1);
+    hw.add(al - 5, 4);
+    int32_t remaining = (int32_t)size + 1, threshold = (int32_t)size;
+    uint32_t nb = al + 1, sym = 0;
+    bool prev0 = false;
+    while (remaining > 1) {
+        if (prev0) {
+            uint32_t run = 0;
+            while (norm[sym] == 0) {
+                sym++;
+                run++;
+            }
+            for (; run >= 3; run -= 3) hw.add(3, 2);
+            hw.add(run, 2);
+            hw.flush();
+        }
+        int32_t c = norm[sym++];
+        const int32_t max = (2 * threshold - 1) - remaining;
+        remaining -= c;
+        prev0 = c == 0;
+        c++;
+        if (c >= threshold) c += max;
+        hw.add((uint32_t)c, nb - (c < max ? 1u : 0u));
+        hw.flush();
+        while (remaining < threshold) {
+            nb--;
+            threshold >>= 1;
+        }
+    }
+    if (hw.nb) {  // the last bits' byte
+        hw.nb = 8;
+        hw.flush();
+    }
+    if (hw.ovf) return 0;
+    const uint32_t nh = hw.n;
+    if (!build_fse_enc(W.t.fstate, W.t.ftt, norm, max_sym, al, W.t.cumul, W.t.tsym)) return 0;
+    BitW sw(d + nh, kHufDescMax - 1 - nh);
+    uint32_t s1 = 0, s2 = 0;  // weights of even index: state 1, of odd index: state 2
+    for (uint32_t i = listed; i-- > 0;) {
+        uint32_t& st = (i & 1) ? s2 : s1;
+        if (i + 2 >= listed) fse_init(st, W.t.ftt, W.t.fstate, w[i]);
+        else fse_put(sw, st, W.t.ftt, W.t.fstate, w[i]);
+        sw.flush();
+    }
+    sw.add(s2, al);
+    sw.add(s1, al);
+    const uint32_t sn = sw.close();
+    return sn ? nh + sn : 0u;
+}
+
+// The tree's description at W.t.desc: the smaller of the direct form (header 127 + listed
+// weights, two weights a byte; up to 128 listed weights) and the FSE form (header: its bytes,
+// below 128). Nothing outside W is written, so the size is known before the section is laid out.
+// Returns the bytes, 0 when neither form can describe the tree.
+NXZ_HD uint32_t write_huf_desc(HufWork& W, const uint8_t* w, uint32_t n_sym) {
+    const uint32_t listed = n_sym - 1;
+    const uint32_t direct = listed <= 128 ? 1 + (listed + 1) / 2 : 0u;
+    const uint32_t fse = huf_fse_weights(W, w, listed);
+    uint8_t* d = W.t.desc;
+    if (fse && (!direct || 1 + fse < direct)) {
+        d[0] = (uint8_t)fse;
+        return 1 + fse;
+    }
+    if (!direct) return 0;
+    d[0] = (uint8_t)(127 + listed);
+    for (uint32_t i = 0; i < listed; i += 2)
+        d[1 + i / 2] = (uint8_t)((w[i] << 4) | (i + 1 < listed ? w[i + 1] : 0));
+    return direct;
+}
+
+// A Huffman form of `desc` description bytes tried against plan p: taken when smaller.
+NXZ_HD bool plan_huf(LitPlan& p, uint32_t n, const uint64_t* bits, uint32_t desc) {
+    if (n < 1024) {
+        const uint32_t cs = desc + huf_stream_bytes(bits[0]);
+        if (cs >= 1024 || 3 + cs >= p.size) return false;
+        p.mode = LIT_HUF1;
+        p.hdr = 3;
+        p.size = 3 + cs;
+        p.ssz[0] = cs - desc;
+        return true;
+    }
+    uint32_t cs = desc + 6;
+    for (int k = 0; k < 4; k++) cs += huf_stream_bytes(bits[k]);
+    const uint32_t hdr = n < 16384 && cs < 16384 ? 4u : 5u;
+    if (hdr + cs >= p.size) return false;
+    p.mode = LIT_HUF4;
+    p.hdr = hdr;
+    p.size = hdr + cs;
+    for (int k = 0; k < 4; k++) p.ssz[k] = huf_stream_bytes(bits[k]);
+    return true;
+}
+// Literals with block trees (kLitBlockTrees). The candidates in order, the earlier on a tie: raw,
+// RLE, treeless with the frame's live tree (`live`: there is one and every literal has a code;
+// this is plan_literals), a Compressed_Literals_Block with the fresh tree (`fresh_ok`: it has a
+// description, of `desc` bytes, which count in the section's compressed size). *fresh: the last
+// was taken, and the block's tree becomes the live one once the block is written.
+NXZ_HD LitPlan plan_literals_trees(uint32_t n, bool all_same, bool live, const uint64_t* bits_live,
+                                   bool fresh_ok, const uint64_t* bits_fresh, uint32_t desc,
+                                   bool* fresh) {
+    LitPlan p = plan_literals(n, all_same, live, bits_live);
+    *fresh = false;
+    if (p.mode == LIT_RLE || !fresh_ok || n < kFreshMinLits) return p;
+    *fresh = plan_huf(p, n, bits_fresh, desc);
+    return p;
+}
+// write_lit_header for a plan of plan_literals_trees: a fresh tree's section is header (type 2),
+// description, jump table, streams.
+NXZ_HD uint32_t write_lit_header_trees(uint8_t* dst, const LitPlan& p, uint32_t n, uint32_t rle_byte,
+                                       bool fresh, const uint8_t* desc, uint32_t dsz) {
+    if (!fresh) return write_lit_header(dst, p, n, rle_byte);
+    const uint32_t cs = p.size - p.hdr;
+    uint64_t h;
+    if (p.mode == LIT_HUF1) h = 2u | (0u << 2) | ((uint64_t)n << 4) | ((uint64_t)cs << 14);
+    else if (p.hdr == 4) h = 2u | (2u << 2) | ((uint64_t)n << 4) | ((uint64_t)cs << 18);
+    else h = 2u | (3u << 2) | ((uint64_t)n << 4) | ((uint64_t)cs << 22);
+    for (uint32_t i = 0; i < p.hdr; i++) dst[i] = (uint8_t)(h >> (8 * i));
+    uint32_t at = p.hdr;
+    for (uint32_t i = 0; i < dsz; i++) dst[at++] = desc[i];
+    if (p.mode == LIT_HUF1) return at;
+    for (int k = 0; k < 3; k++) {
+        dst[at++] = (uint8_t)p.ssz[k];
+        dst[at++] = (uint8_t)(p.ssz[k] >> 8);
+    }
+    return at;
 }
 
 // ---- frame and block headers --------------------------------------------------------------------

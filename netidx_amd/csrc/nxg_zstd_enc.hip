@@ -23,6 +23,12 @@
 //     stream by lane 0 up to 1023 literals, else four streams by lanes 0..3, from literals the
 //     wave stages in LDS) when every literal has a code and that is smaller, else raw. The streams' sizes follow from the code lengths'
 //     sums, counted by the whole wave, so every stream's place is known before it is written;
+//     With block trees (NxgZstdCompressOpts.literals = 1, the kernel's second instantiation) the
+//     same pass takes the literals' histogram (LDS atomics); the wave sorts the counts, lane 0
+//     builds code lengths of at most 11 bits, the codes and the tree's description
+//     (nxg_zstd_enc.h), a second pass sums the streams' bits under them, and the block's own tree
+//     (Compressed_Literals_Block) is one more candidate after raw, RLE and the treeless form with
+//     the frame's live tree -- the dictionary's until a block of the frame writes its own;
 //   sequences section: predefined distributions, FSE-encoded by lane 0 (nxg_zstd_enc.h);
 //   a block whose compressed form is not smaller than its bytes is a raw block.
 // Every store is bounded by the record's slot: the compressed form is written under a byte limit
@@ -69,6 +75,29 @@ struct ELds {
     uint8_t stage[4][HCH];
     EncTables enc;  // the predefined distributions' encoding tables, next to the lane that codes
 };
+// with block trees (kLitBlockTrees): `codes` is the frame's live tree; the tree build's working
+// memory lies over the literal stage, which is idle until the streams are written; the block's
+// own codes and weights take 1280 of the 2064 bytes ELds leaves of a quarter of the CU's LDS
+struct ELdsTrees {
+    uint32_t ht[1u << HBITS];
+    HufCode codes[256];
+    union {
+        uint8_t stage[4][HCH];
+        HufWork work;
+    };
+    EncTables enc;
+    HufCode fresh[256];
+    uint8_t w[256];
+};
+static_assert(sizeof(ELdsTrees) == sizeof(ELds) + 1280, "the stage and the tree build share");
+template <uint32_t MODE>
+struct LdsOf {
+    using T = ELds;
+};
+template <>
+struct LdsOf<kLitBlockTrees> {
+    using T = ELdsTrees;
+};
 
 NXG_DEV uint32_t bcast(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 NXG_DEV uint8_t ldnt(const uint8_t* p) { return __builtin_nontemporal_load(p); }
@@ -103,13 +132,43 @@ NXG_DEV void copy_bytes(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t
     for (uint32_t k = lane; k < len; k += 64) dst[k] = NT ? ldnt(src + k) : src[k];
 }
 
+// huf_sort_hist by the whole wave: a lane ranks its four symbols' keys among all 256 (the keys of
+// present symbols are distinct, so the ranks are their places) and writes count and symbol there.
+// Returns the present symbols.
+NXG_DEV uint32_t sort_hist_wave(HufWork& W, uint32_t lane) {
+    wave_lds_order();
+    uint32_t key[4], rank[4] = {0, 0, 0, 0}, n = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        const uint32_t s = lane + 64 * j, c = W.hist[s];
+        key[j] = c ? (c << 8) | s : ~0u;
+        n += (uint32_t)__popcll(__ballot(c != 0));
+    }
+    for (uint32_t t = 0; t < 256; t++) {
+        const uint32_t c = W.hist[t], kt = c ? (c << 8) | t : ~0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++) rank[j] += kt < key[j] ? 1u : 0u;
+    }
+    wave_lds_order();  // the symbols' places lie over the counts: every lane has read them
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++)
+        if (key[j] != ~0u) {
+            W.a[rank[j]] = key[j] >> 8;
+            W.t.ord[rank[j]] = (uint8_t)key[j];
+        }
+    wave_lds_order();
+    return n;
+}
+
 // The Huffman streams of a block's literals at `base`: ns = 1 (lane 0) or 4 (lanes 0..3, stream k
 // = the literals [k * seg, ...)). A lane's loads from the literal buffer would each wait out a
 // trip to L2, so the wave stages every stream's next HCH literals (from its end backwards, the
 // order they are coded in) in LDS and the coding lanes read them there. True when every stream
 // took exactly the bytes planned for it.
-NXG_DEV bool huf_streams(ELds& L, uint8_t* base, const LitPlan& plan, const uint8_t* lit,
-                         uint32_t nlit, uint32_t seg, uint32_t ns, uint32_t lane) {
+template <typename LT>
+NXG_DEV bool huf_streams(LT& L, const HufCode* codes, uint8_t* base, const LitPlan& plan,
+                         const uint8_t* lit, uint32_t nlit, uint32_t seg, uint32_t ns,
+                         uint32_t lane) {
     uint32_t so = 0, sz = 0, cnt = 0;
     if (ns == 1) {
         sz = plan.ssz[0];
@@ -135,7 +194,7 @@ NXG_DEV bool huf_streams(ELds& L, uint8_t* base, const LitPlan& plan, const uint
             for (uint32_t j = lane; j < take; j += 64) L.stage[k][j] = ldnt(s + j);
         }
         wave_lds_order();
-        if (coder && done < cnt) huf_put(w, &L.stage[lane][0], min(HCH, cnt - done), L.codes, LdsB{});
+        if (coder && done < cnt) huf_put(w, &L.stage[lane][0], min(HCH, cnt - done), codes, LdsB{});
     }
     wave_lds_order();
     bool ok = true;
@@ -144,10 +203,13 @@ NXG_DEV bool huf_streams(ELds& L, uint8_t* base, const LitPlan& plan, const uint
 }
 
 // One block [b0, b1) of the record at dst (its 3-byte header first); returns the bytes written.
-// `room` >= 3 + (b1 - b0) bytes are the caller's to give.
-NXG_DEV uint32_t compress_block(ELds& L, const Src& S, uint64_t b0, uint64_t b1, bool coded_dict,
-                                const EncTables* T, uint8_t* dst, uint8_t* lit, uint64_t* seqs,
-                                bool last, uint32_t lane) {
+// `room` >= 3 + (b1 - b0) bytes are the caller's to give. `coded_dict`: L.codes holds a tree the
+// frame's reader has (the dictionary's; with block trees the live one, which a block that writes
+// its own tree replaces).
+template <uint32_t MODE>
+NXG_DEV uint32_t compress_block(typename LdsOf<MODE>::T& L, const Src& S, uint64_t b0, uint64_t b1,
+                                bool& coded_dict, const EncTables* T, uint8_t* dst, uint8_t* lit,
+                                uint64_t* seqs, bool last, uint32_t lane) {
     const uint32_t blen = (uint32_t)(b1 - b0);
     const uint8_t* blk = S.s + b0;
     // ---- one repeated byte: an RLE block
@@ -240,9 +302,14 @@ NXG_DEV uint32_t compress_block(ELds& L, const Src& S, uint64_t b0, uint64_t b1,
     uint32_t bsum0 = 0, bsum1 = 0, bsum2 = 0, bsum3 = 0;
     bool same = true, coded = coded_dict;
     const uint32_t lit0 = nlit ? ldnt(lit) : 0u;
+    if constexpr (MODE == kLitBlockTrees) {  // the literals' histogram, taken in the same pass
+        for (uint32_t i = lane; i < 256; i += 64) L.work.hist[i] = 0;
+        wave_lds_order();
+    }
     for (uint32_t i = lane; i < nlit; i += 64) {
         const uint32_t b = ldnt(lit + i);
         same &= b == lit0;
+        if constexpr (MODE == kLitBlockTrees) atomicAdd(&L.work.hist[b], 1u);
         if (coded_dict) {
             const uint32_t nb = L.codes[b].nbits;
             coded &= nb != 0;
@@ -257,21 +324,63 @@ NXG_DEV uint32_t compress_block(ELds& L, const Src& S, uint64_t b0, uint64_t b1,
     coded = !__any(!coded);
     uint64_t bits[4] = {wave_sum<uint32_t>(bsum0), wave_sum<uint32_t>(bsum1),
                         wave_sum<uint32_t>(bsum2), wave_sum<uint32_t>(bsum3)};
-    const LitPlan plan = plan_literals(nlit, same, coded, bits);
+    LitPlan plan;
+    bool fresh = false;  // the literals take the block's own tree
+    uint32_t dsz = 0;    // its description's bytes (L.work.t.desc)
+    const HufCode* codes = L.codes;
+    if constexpr (MODE == kLitBlockTrees) {
+        uint64_t fbits[4] = {0, 0, 0, 0};
+        if (!same && nlit >= kFreshMinLits) {
+            const uint32_t nsym = sort_hist_wave(L.work, lane);  // >= 2: the literals differ
+            if (lane == 0) {  // <= 256 symbols, serial: lengths, codes, description
+                uint32_t ns = 0, mb = 0;
+                huf_build_weights(L.work, nsym, L.w, &ns, &mb);
+                build_huf_enc_ws(L.fresh, L.w, ns, mb, L.work.a, L.work.a + kHufMaxBits + 2);
+                dsz = write_huf_desc(L.work, L.w, ns);
+            }
+            dsz = bcast(dsz);
+            wave_lds_order();
+            if (dsz) {  // the streams' bits under the block's own codes: a second pass
+                uint32_t f0 = 0, f1 = 0, f2 = 0, f3 = 0;
+                for (uint32_t i = lane; i < nlit; i += 64) {
+                    const uint32_t nb = L.fresh[ldnt(lit + i)].nbits;
+                    const uint32_t k = i / seg;
+                    f0 += k == 0 ? nb : 0u;
+                    f1 += k == 1 ? nb : 0u;
+                    f2 += k == 2 ? nb : 0u;
+                    f3 += k == 3 ? nb : 0u;
+                }
+                fbits[0] = wave_sum<uint32_t>(f0);
+                fbits[1] = wave_sum<uint32_t>(f1);
+                fbits[2] = wave_sum<uint32_t>(f2);
+                fbits[3] = wave_sum<uint32_t>(f3);
+            }
+        }
+        plan = plan_literals_trees(nlit, same, coded, bits, dsz != 0, fbits, dsz, &fresh);
+        if (fresh) codes = L.fresh;
+    } else {
+        plan = plan_literals(nlit, same, coded, bits);
+    }
     // ---- the compressed form, under blen - 1 bytes; else the raw block
     uint32_t body = 0;  // 0: raw
     if ((uint64_t)plan.size + 1 <= blen - 1) {
         uint8_t* lp = dst + 3;
         uint32_t at = 0;
-        if (lane == 0) at = write_lit_header(lp, plan, nlit, lit0);
+        if constexpr (MODE == kLitBlockTrees) {
+            if (lane == 0)
+                at = write_lit_header_trees(lp, plan, nlit, lit0, fresh, L.work.t.desc, dsz);
+            wave_lds_order();  // the description is out before the stage takes its bytes
+        } else {
+            if (lane == 0) at = write_lit_header(lp, plan, nlit, lit0);
+        }
         at = bcast(at);
         bool ok = true;
         if (plan.mode == LIT_RAW) {
             copy_bytes<true>(lp + at, lit, nlit, lane);
         } else if (plan.mode == LIT_HUF1) {
-            ok = huf_streams(L, lp + at, plan, lit, nlit, seg, 1, lane);
+            ok = huf_streams(L, codes, lp + at, plan, lit, nlit, seg, 1, lane);
         } else if (plan.mode == LIT_HUF4) {
-            ok = huf_streams(L, lp + at, plan, lit, nlit, seg, 4, lane);
+            ok = huf_streams(L, codes, lp + at, plan, lit, nlit, seg, 4, lane);
         }
         ok = !__any(!ok);
         if (ok) {
@@ -289,6 +398,14 @@ NXG_DEV uint32_t compress_block(ELds& L, const Src& S, uint64_t b0, uint64_t b1,
     }
     if (body) {
         if (lane == 0) write_block_header(dst, 2, body, last);
+        if constexpr (MODE == kLitBlockTrees) {
+            if (fresh) {  // the reader's tree from here on, until a block writes another
+                wave_lds_order();
+                for (uint32_t i = lane; i < 256; i += 64) L.codes[i] = L.fresh[i];
+                wave_lds_order();
+                coded_dict = true;
+            }
+        }
         return 3 + body;
     }
     drain();  // lane 0's stores of the dropped form land before the raw bytes
@@ -297,6 +414,9 @@ NXG_DEV uint32_t compress_block(ELds& L, const Src& S, uint64_t b0, uint64_t b1,
     return 3 + blen;
 }
 
+// MODE: NxgZstdCompressOpts.literals (kLitDictTree: the dictionary's tree only; kLitBlockTrees:
+// a block may write its own)
+template <uint32_t MODE>
 __global__ __launch_bounds__(64) void nxg_zstd_enc_kernel(const uint8_t* __restrict__ src,
                                                           const NxzEncRec* __restrict__ recs,
                                                           uint32_t n, const NxzEncDict* dict,
@@ -304,7 +424,7 @@ __global__ __launch_bounds__(64) void nxg_zstd_enc_kernel(const uint8_t* __restr
                                                           uint8_t* slab, NxzEncRes* res,
                                                           const uint32_t* __restrict__ order,
                                                           uint32_t* ticket) {
-    __shared__ __attribute__((aligned(16))) ELds L;
+    __shared__ __attribute__((aligned(16))) typename LdsOf<MODE>::T L;
     const uint32_t lane = threadIdx.x;
     uint8_t* lit = slab + (uint64_t)blockIdx.x * SLAB;
     uint64_t* seqs = reinterpret_cast<uint64_t*>(lit + kBlockMax);
@@ -340,10 +460,17 @@ __global__ __launch_bounds__(64) void nxg_zstd_enc_kernel(const uint8_t* __restr
             if (lane == 0) write_block_header(dst + op, 0, 0, true);
             op += 3;
         }
+        bool live = coded_dict;  // a frame starts from the dictionary's tree, or none
+        if constexpr (MODE == kLitBlockTrees) {  // the last frame may have left its own in L.codes
+            if (coded_dict) {
+                for (uint32_t i = lane; i < 256; i += 64) L.codes[i] = dict->codes[i];
+                wave_lds_order();
+            }
+        }
         for (uint64_t b0 = 0; b0 < S.n; b0 += kBlockMax) {
             const uint64_t b1 = S.n - b0 > kBlockMax ? b0 + kBlockMax : S.n;
-            op += compress_block(L, S, b0, b1, coded_dict, &L.enc, dst + op, lit, seqs, b1 == S.n,
-                                 lane);
+            op += compress_block<MODE>(L, S, b0, b1, live, &L.enc, dst + op, lit, seqs, b1 == S.n,
+                                       lane);
         }
         if (lane == 0) res[r] = NxzEncRes{op, 0, 0};
         wave_lds_order();
@@ -415,7 +542,9 @@ uint64_t nxg_zstd_dict_table_bytes() { return sizeof(uint32_t) << DBITS; }
 uint64_t nxg_zstd_frame_bound(uint64_t len) { return frame_bound(len); }
 int nxg_zstd_enc_grid(int ncu) {
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nxg_zstd_enc_kernel, 64, 0) != hipSuccess)
+    // both instantiations hold four workgroups per CU (by LDS); the grid sizes the slab once
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nxg_zstd_enc_kernel<kLitDictTree>, 64,
+                                                     0) != hipSuccess)
         occ = 1;
     return std::min(4, std::max(1, occ)) * ncu;
 }
@@ -432,10 +561,13 @@ hipError_t nxg_launch_zstd_dict_hash(const uint8_t* dcontent, uint32_t content_l
 hipError_t nxg_launch_zstd_enc(const uint8_t* dsrc, const void* drecs, uint32_t n,
                                const void* ddict, const void* dtables, uint8_t* dout,
                                uint8_t* dslab, void* dres, const uint32_t* dorder,
-                               uint32_t* dticket, int grid, hipStream_t s) {
+                               uint32_t* dticket, int grid, uint32_t literals, hipStream_t s) {
     if (n == 0) return hipSuccess;
+    if (literals > kLitBlockTrees) return hipErrorInvalidValue;  // no kernel for it: an error
     const uint32_t g = (uint32_t)std::min<uint64_t>((uint64_t)grid, n);
-    hipLaunchKernelGGL(nxg_zstd_enc_kernel, dim3(g), dim3(64), 0, s, dsrc,
+    auto k = literals == kLitBlockTrees ? nxg_zstd_enc_kernel<kLitBlockTrees>
+                                        : nxg_zstd_enc_kernel<kLitDictTree>;
+    hipLaunchKernelGGL(k, dim3(g), dim3(64), 0, s, dsrc,
                        reinterpret_cast<const NxzEncRec*>(drecs), n,
                        reinterpret_cast<const NxzEncDict*>(ddict),
                        reinterpret_cast<const EncTables*>(dtables), dout, dslab,
@@ -460,10 +592,9 @@ hipError_t nxg_launch_zstd_pack(const uint8_t* dout, const void* drecs, const vo
 // may be null. Returns the frame's bytes, 0 when `cap` is below nxg_zstd_frame_bound(n) or the
 // dictionary does not parse. The device's parse differs (64 positions per step): its frames are
 // pinned by tests/golden/zstd_gpu_records.bin.
-extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t dlen,
-                                                 const uint8_t* src, uint64_t n, uint8_t* out,
-                                                 uint64_t cap) {
-    if (cap < frame_bound(n) || n >= (1ull << 32)) return 0;
+static uint64_t compress_host(const uint8_t* dict, uint64_t dlen, const uint8_t* src, uint64_t n,
+                              uint8_t* out, uint64_t cap, uint32_t literals) {
+    if (cap < frame_bound(n) || n >= (1ull << 32) || literals > kLitBlockTrees) return 0;
     NxzEncDict ed;
     memset(&ed, 0, sizeof ed);
     const uint8_t* dc = nullptr;
@@ -495,6 +626,10 @@ extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t d
     }
     std::vector<uint8_t> lit(kBlockMax);
     std::vector<uint64_t> seqs(NSEQ_MAX);
+    bool live = ed.has_tables != 0;  // ed.codes is a tree the frame's reader has
+    HufWork W;
+    uint8_t fw[256];
+    HufCode fcodes[256];
     auto hb = [&](uint64_t k, uint32_t off) -> uint8_t {
         return k >= off ? src[k - off] : dc[dl - (uint32_t)(off - k)];
     };
@@ -548,30 +683,51 @@ extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t d
         const bool four = nlit >= 1024;
         const uint32_t seg = four ? (nlit + 3) / 4 : (nlit ? nlit : 1u);
         uint64_t bits[4] = {0, 0, 0, 0};
-        bool lsame = true, coded = ed.has_tables != 0;
+        bool lsame = true, coded = live;
         for (uint32_t i = 0; i < nlit; i++) {
             lsame &= lit[i] == lit[0];
             const uint32_t nb = ed.codes[lit[i]].nbits;
             coded &= nb != 0;
             bits[i / seg] += nb;
         }
-        const LitPlan plan = plan_literals(nlit, lsame, coded, bits);
+        LitPlan plan;
+        bool fresh = false;
+        uint32_t dsz = 0;
+        const HufCode* codes = ed.codes;  // the live tree
+        if (literals == kLitBlockTrees) {
+            uint64_t fbits[4] = {0, 0, 0, 0};
+            if (!lsame && nlit >= kFreshMinLits) {
+                memset(W.hist, 0, sizeof W.hist);
+                for (uint32_t i = 0; i < nlit; i++) W.hist[lit[i]]++;
+                const uint32_t nsym = huf_sort_hist(W);
+                uint32_t ns = 0, mb = 0;
+                huf_build_weights(W, nsym, fw, &ns, &mb);
+                build_huf_enc_ws(fcodes, fw, ns, mb, W.a, W.a + kHufMaxBits + 2);
+                dsz = write_huf_desc(W, fw, ns);
+                for (uint32_t i = 0; dsz && i < nlit; i++) fbits[i / seg] += fcodes[lit[i]].nbits;
+            }
+            plan = plan_literals_trees(nlit, lsame, coded, bits, dsz != 0, fbits, dsz, &fresh);
+            if (fresh) codes = fcodes;
+        } else {
+            plan = plan_literals(nlit, lsame, coded, bits);
+        }
         uint32_t body = 0;
         if ((uint64_t)plan.size + 1 <= blen - 1) {
             uint8_t* lp = dst + 3;
-            const uint32_t at = write_lit_header(lp, plan, nlit, nlit ? lit[0] : 0);
+            const uint32_t at = write_lit_header_trees(lp, plan, nlit, nlit ? lit[0] : 0, fresh,
+                                                       W.t.desc, dsz);
             bool ok = true;
             if (plan.mode == LIT_RAW) {
                 memcpy(lp + at, lit.data(), nlit);
             } else if (plan.mode == LIT_HUF1) {
-                ok = huf_encode_stream(lp + at, plan.ssz[0], lit.data(), nlit, ed.codes,
+                ok = huf_encode_stream(lp + at, plan.ssz[0], lit.data(), nlit, codes,
                                        PlainB{}) == plan.ssz[0];
             } else if (plan.mode == LIT_HUF4) {
                 uint32_t so = 0;
                 for (uint32_t k = 0; k < 4; k++) {
                     const uint32_t c = k < 3 ? seg : nlit - 3 * seg;
                     ok &= huf_encode_stream(lp + at + so, plan.ssz[k], lit.data() + k * seg, c,
-                                            ed.codes, PlainB{}) == plan.ssz[k];
+                                            codes, PlainB{}) == plan.ssz[k];
                     so += plan.ssz[k];
                 }
             }
@@ -587,6 +743,10 @@ extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t d
         if (body) {
             write_block_header(dst, 2, body, last);
             op += 3 + body;
+            if (fresh) {  // the frame's live tree from here on
+                memcpy(ed.codes, fcodes, sizeof fcodes);
+                live = true;
+            }
         } else {
             write_block_header(dst, 0, blen, last);
             memcpy(dst + 3, src + b0, blen);
@@ -594,6 +754,47 @@ extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t d
         }
     }
     return op;
+}
+extern "C" uint64_t nxg_debug_zstd_compress_host(const uint8_t* dict, uint64_t dlen,
+                                                 const uint8_t* src, uint64_t n, uint8_t* out,
+                                                 uint64_t cap) {
+    return compress_host(dict, dlen, src, n, out, cap, kLitDictTree);
+}
+// the same with NxgZstdCompressOpts.literals (0 also for a value the library does not know)
+extern "C" uint64_t nxg_debug_zstd_compress_host_opts(const uint8_t* dict, uint64_t dlen,
+                                                      const uint8_t* src, uint64_t n,
+                                                      uint32_t literals, uint8_t* out,
+                                                      uint64_t cap) {
+    return compress_host(dict, dlen, src, n, out, cap, literals);
+}
+
+// Not part of the ABI (tests, host only, no GPU): the code builder and the tree description
+// writer of a block's own Huffman tree (nxg_zstd_enc.h), as the device and the host-only encoder
+// run them. huf_weights: a 256-entry histogram -> w[256] (0: absent); returns the symbols listed
+// (the last present symbol + 1; 0 when fewer than two symbols are present), *max_bits the longest
+// code. huf_desc: the weights of n_sym symbols -> the description at out (at least 132 bytes);
+// returns its bytes, 0 when no form can describe the tree.
+extern "C" uint32_t nxg_debug_zstd_huf_weights(const uint32_t* hist, uint8_t* w,
+                                               uint32_t* max_bits) {
+    HufWork W;
+    uint64_t total = 0;
+    for (uint32_t s = 0; s < 256; s++) total += hist[s];
+    if (total > kBlockMax) return 0;  // a block's literals: the sort's keys hold 24-bit counts
+    memcpy(W.hist, hist, sizeof W.hist);
+    const uint32_t n = huf_sort_hist(W);
+    if (n < 2) return 0;
+    uint32_t ns = 0;
+    huf_build_weights(W, n, w, &ns, max_bits);
+    return ns;
+}
+extern "C" uint32_t nxg_debug_zstd_huf_desc(const uint8_t* w, uint32_t n_sym, uint8_t* out) {
+    if (n_sym < 2 || n_sym > 256) return 0;
+    for (uint32_t i = 0; i < n_sym; i++)
+        if (w[i] > kHufEncBits) return 0;
+    HufWork W;
+    const uint32_t n = write_huf_desc(W, w, n_sym);
+    memcpy(out, W.t.desc, n);
+    return n;
 }
 
 // Not part of the ABI (tests, host only, no GPU): one frame (no dictionary) of one compressed
