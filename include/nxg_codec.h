@@ -220,8 +220,9 @@ bool nxg_encode_frames(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, u
  * mean for an Update, and the two further fields of a Write go to the companion NxgWriteCols
  * (NxgColumns keeps its layout). Subscribe and Unsubscribe messages are validated and kept as raw
  * control spans (ctl_row/ctl_off/ctl_len) with ctl_variant = the To variant (0 or 1).
- * Synchronous calls only: the async ring, the multi-GPU calls and the sessions do not take To
- * frames. */
+ * nxg_route_writes (below) then routes the decoded rows: permissions, on_write channels, the
+ * WriteResult and Unsubscribed replies. Synchronous calls only: the async ring, the multi-GPU
+ * calls and the sessions do not take To frames. */
 #define NXG_PATH_WRITES 6 /* NxgStatus.path of a To-frame decode */
 enum NxgWriteFlags {
     NXG_WRITE_REPLY = 1, /* Write's bool: the writer wants a WriteResult */
@@ -403,6 +404,108 @@ typedef struct NxgDispatch {
  * a HIP failure, or entries > cap_entries (n_entries then holds the required capacity). */
 bool nxg_dispatch_updates(NxgCtx* ctx, const NxgSubTable* tab, const uint64_t* id,
                           uint64_t n_rows, NxgDispatch* out, NetidxError* err);
+
+/* ---- write routing: replaces the Write and Unsubscribe arms of ClientCtx::handle_batch_inner
+ * (netidx/src/publisher/server.rs:497-576) and write() (server.rs:171-245) ----------------------
+ * The rows and control spans of one decoded To frame (nxg_decode_writes, device columns), in
+ * message order, with the reference's outcome per message. State is per connection (client).
+ * For Write(id, r, v, wid), row i, the checks run in this order:
+ *   NXG_WRITE_UNSUBSCRIBED  the client is not subscribed to id, "cannot write to unsubscribed
+ *       value" (server.rs:201-202): id >= n_ids, perm_of_id[id] == NXG_NOT_SUBSCRIBED, or an
+ *       Unsubscribe(id) came earlier in this batch (server.rs:562-565; unsubscribe() removes
+ *       cl.subscribed[id]). A client the publisher does not know gets the same message
+ *       (server.rs:201): pass a table with n_ids = 0.
+ *   NXG_WRITE_DENIED        the permissions lack WRITE (0x04, resolver_server/auth.rs:26), "write
+ *       permission denied" (server.rs:203-205)
+ *   NXG_WRITE_NOT_ACCEPTED  no on_write entry for id, or none of its channels is open, "writes
+ *       not accepted" (server.rs:206-217). The host builds the table from open channels only (the
+ *       retain of server.rs:207-214; it keeps its own gc_on_write), so a slot with an empty channel
+ *       list is this outcome.
+ *   NXG_WRITE_ROUTED        one request onto each channel of on_write[id], in list order
+ *       (server.rs:225-240); with r set, (id, wid) is appended to the wait list (server.rs:218-224).
+ *       The table describes published values only: an on_write slot implies that by_id has the Id
+ *       (the `if let Some(pbv) = t.by_id.get(&id)` of server.rs:226 always holds).
+ * The other three outcomes with r set queue From::WriteResult(id, Error(String(msg)), wid) on the
+ * connection (server.rs:191-194); without r they queue nothing. Unsubscribe(id) always queues
+ * From::Unsubscribed(id), for any id, subscribed or not (server.rs:562-566).
+ * Order: control span k precedes row ctl_row[k]; spans with equal ctl_row are in k order; a write
+ * at row i is after an Unsubscribe span k if and only if ctl_row[k] <= i. The reply frame holds
+ * the replies of both kinds in message order:
+ *   Unsubscribed(id)                        varint(L) 02 varint(id)
+ *   WriteResult(id, Error(String(m)), wid)  varint(L) 06 varint(id) 12 varint(|m|) m varint(wid)
+ * The effective WriteId: a row with NXG_WRITE_NO_WID has none on the wire and the reference allots
+ * a fresh one at decode time (WriteId::default() is WriteId::new(), netidx-netproto/src/
+ * publisher.rs:11-15). The caller passes fresh_wid, the first of a block it reserved: among the
+ * rows the call processes, the j-th NO_WID row in row order gets fresh_wid + j, and n_fresh says
+ * how many were used. Replies and the wait list carry the effective id; the columns are not
+ * modified.
+ * Subscribe needs a path lookup and stays with the host: the call stops in front of the first
+ * Subscribe span at or after ctl_begin and says where (below). Also left to the host: creating
+ * the SendResult of each wait-list entry, gc_on_write, its own unsubscribe() bookkeeping from
+ * unsub_id[], and building the WriteRequests (path, client, value) from the entries.
+ *
+ * The table, built by the host for one client; every array is device memory: */
+#define NXG_NOT_SUBSCRIBED 0xffffffffu
+typedef struct NxgWriteTable {
+    uint64_t n_ids;                /* perm_of_id and slot_of_id cover Ids [0, n_ids) */
+    const uint32_t* perm_of_id;    /* [n_ids]: the client's Permissions bits for the Id
+                                      (cl.subscribed[id]), or NXG_NOT_SUBSCRIBED */
+    const uint32_t* slot_of_id;    /* [n_ids]: on_write slot of the Id, or NXG_NO_SLOT */
+    uint64_t n_slots;              /* on_write entries */
+    const uint32_t* slot_chan_off; /* [n_slots + 1]: the slot's open channels, CSR */
+    const uint32_t* chan;          /* open channels in on_write order, each < n_chans */
+    uint32_t n_chans;              /* channels (ChanId) */
+} NxgWriteTable;
+enum NxgWriteOutcome {
+    NXG_WRITE_ROUTED = 0,
+    NXG_WRITE_UNSUBSCRIBED = 1,
+    NXG_WRITE_DENIED = 2,
+    NXG_WRITE_NOT_ACCEPTED = 3
+};
+/* Capacities and device arrays from the caller, counts written by the call. A-priori bounds for
+ * R rows and K control spans: entries <= R * the longest channel list, wait <= R, unsub <= K,
+ * reply bytes <= 58 * R + 12 * K. */
+typedef struct NxgWriteRoute {
+    uint64_t cap_rows;  /* outcome[] entries, >= cols->n_rows */
+    uint8_t* outcome;   /* [cap_rows]: NxgWriteOutcome of row i, written for the processed rows */
+    /* per channel c the requests [chan_off[c], chan_off[c+1]) as (ent_sub = Id, ent_row = row in
+     * the columns), in batch order; chan_off has n_chans + 1 entries; last_row is not used (NULL);
+     * n_entries is repeated below, n_unmatched is 0 */
+    NxgDispatch disp;
+    uint64_t cap_wait;  /* wait list: (row, Id, effective WriteId) of routed rows with r set */
+    uint64_t* wait_row;
+    uint64_t* wait_id;
+    uint64_t* wait_wid;
+    uint64_t cap_unsub; /* the Ids of the Unsubscribe spans, in order */
+    uint64_t* unsub_id;
+    uint64_t cap_reply; /* the reply frame's payload */
+    uint8_t* reply;
+    /* written by the call */
+    uint64_t n_entries, n_wait, n_unsub;
+    uint64_t n_replies;    /* messages in `reply` (WriteResults + Unsubscribeds) */
+    uint64_t reply_len;    /* bytes in `reply` */
+    uint64_t n_fresh;      /* WriteIds taken from fresh_wid on */
+    uint64_t n_outcome[4]; /* processed rows per NxgWriteOutcome */
+    uint64_t next_row, next_ctl; /* where to resume: row_begin / ctl_begin of the next call */
+    uint32_t stopped_at_subscribe; /* 1: span next_ctl - 1 is a Subscribe, in front of next_row */
+    uint32_t pad;
+} NxgWriteRoute;
+/* `frame` is the device frame the columns were decoded from (the Unsubscribe spans' Ids are read
+ * from it: varint(L) 01 varint(id), validated by the decode; a non-canonical L and trailing bytes
+ * inside the wrap are accepted as the decode accepted them). `cols` / `wcols`: the device columns
+ * nxg_decode_writes filled. The call processes control spans [ctl_begin, s), s = the first
+ * Subscribe span at or after ctl_begin or n_ctl, and rows [row_begin, ctl_row[s]) or to n_rows. On
+ * return next_ctl = s + 1 and next_row = ctl_row[s], or both are at the end and
+ * stopped_at_subscribe is 0: the host handles the Subscribe, updates the table (the unsub_id[] of
+ * this call included) and calls again with (next_row, next_ctl) until next_ctl == n_ctl and
+ * next_row == n_rows. A call covers fewer than 2^32 rows. One synchronisation; synchronous.
+ * Returns false on misuse (the message names the field: host or F64-layout columns, wcols NULL,
+ * row_begin / ctl_begin past the end, a missing array), on a HIP failure, or when a capacity is
+ * exceeded; the counts then hold the required values (n_entries, n_wait, n_unsub, reply_len), as
+ * nxg_dispatch_updates does, and the arrays hold what fitted. */
+bool nxg_route_writes(NxgCtx* ctx, const NxgWriteTable* tab, const uint8_t* frame,
+                      const NxgColumns* cols, const NxgWriteCols* wcols, uint64_t row_begin,
+                      uint64_t ctl_begin, uint64_t fresh_wid, NxgWriteRoute* out, NetidxError* err);
 
 /* ---- type-partitioned view of decoded mixed columns (optional output) --------
  * Replaces the per-value 28-way `match` on the tag (Value::decode, netidx-value/src/lib.rs:470-506)

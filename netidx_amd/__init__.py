@@ -14,7 +14,9 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     msg_subscribe, msg_subscribed, msg_heartbeat, msg_parse, msg_update,
                     TAG_UNSUBSCRIBED, Resolver, ResolverClient, TagView, TAG_BINS, WriteCols,
                     NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES, ArchiveImage,
-                    WindowCapacity)
+                    WindowCapacity, WriteTable, WriteRoute, RouteCapacity, NOT_SUBSCRIBED,
+                    PERM_WRITE, WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED,
+                    WRITE_NOT_ACCEPTED)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
            "frame_split", "frame_header", "frame_parse_header", "LAYOUT_F64", "LAYOUT_MIXED",
@@ -24,4 +26,6 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "Comm", "NxgRange", "range_link", "Session", "msg_subscribe", "msg_subscribed",
            "msg_heartbeat", "msg_parse", "msg_update", "TAG_UNSUBSCRIBED", "Resolver",
            "ResolverClient", "TagView", "TAG_BINS", "WriteCols", "NxgWriteCols", "WRITE_REPLY",
-           "WRITE_NO_WID", "PATH_WRITES", "ArchiveImage", "WindowCapacity"]
+           "WRITE_NO_WID", "PATH_WRITES", "ArchiveImage", "WindowCapacity", "WriteTable",
+           "WriteRoute", "RouteCapacity", "NOT_SUBSCRIBED", "PERM_WRITE", "WRITE_ROUTED",
+           "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED"]

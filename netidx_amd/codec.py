@@ -102,6 +102,24 @@ class NxgDispatch(C.Structure):
                 ("n_unmatched", C.c_uint64)]
 
 
+class NxgWriteTable(C.Structure):
+    _fields_ = [("n_ids", C.c_uint64), ("perm_of_id", C.c_void_p), ("slot_of_id", C.c_void_p),
+                ("n_slots", C.c_uint64), ("slot_chan_off", C.c_void_p), ("chan", C.c_void_p),
+                ("n_chans", C.c_uint32)]
+
+
+class NxgWriteRoute(C.Structure):
+    _fields_ = [("cap_rows", C.c_uint64), ("outcome", C.c_void_p), ("disp", NxgDispatch),
+                ("cap_wait", C.c_uint64), ("wait_row", C.c_void_p), ("wait_id", C.c_void_p),
+                ("wait_wid", C.c_void_p), ("cap_unsub", C.c_uint64), ("unsub_id", C.c_void_p),
+                ("cap_reply", C.c_uint64), ("reply", C.c_void_p),
+                ("n_entries", C.c_uint64), ("n_wait", C.c_uint64), ("n_unsub", C.c_uint64),
+                ("n_replies", C.c_uint64), ("reply_len", C.c_uint64), ("n_fresh", C.c_uint64),
+                ("n_outcome", C.c_uint64 * 4), ("next_row", C.c_uint64),
+                ("next_ctl", C.c_uint64), ("stopped_at_subscribe", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
 TAG_BINS = 256
 
 
@@ -217,6 +235,10 @@ SIGNATURES = {
     "nxg_encode_writes": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.POINTER(NxgWriteCols),
                                      C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                      C.POINTER(NetidxError)]),
+    "nxg_route_writes": (C.c_bool, [C.c_void_p, C.POINTER(NxgWriteTable), C.c_void_p,
+                                    C.POINTER(NxgColumns), C.POINTER(NxgWriteCols), C.c_uint64,
+                                    C.c_uint64, C.c_uint64, C.POINTER(NxgWriteRoute),
+                                    C.POINTER(NetidxError)]),
     "nxg_decode_range": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                     C.POINTER(NxgColumns), C.POINTER(NxgRange),
                                     C.POINTER(NetidxError)]),
@@ -933,6 +955,59 @@ class Codec:
             assert m == n
         return out[:n]
 
+    def route_writes(self, table, frame, cols, wcols, row_begin=0, ctl_begin=0, fresh_wid=0,
+                     cap_entries=None, cap_wait=None, cap_unsub=None, cap_reply=None):
+        """handle_batch_inner's Write and Unsubscribe arms (publisher/server.rs:171-245, 497-576)
+        for a decoded To frame: `frame` is the device tensor decode_writes read, `cols` / `wcols`
+        what it returned, `table` a WriteTable. Processes rows and control spans from (row_begin,
+        ctl_begin) up to the first Subscribe span and returns a WriteRoute (outcome per row,
+        per-channel requests, the reply frame, the wait list, the unsubscribed Ids, next_row /
+        next_ctl to resume from). Capacities default to the a-priori bounds; one that is exceeded
+        raises RouteCapacity carrying the required counts."""
+        import torch
+        dev = cols.device
+        n_rows, n_ctl = int(cols.s.n_rows), int(cols.s.n_ctl)
+        rows, spans = max(n_rows - row_begin, 0), max(n_ctl - ctl_begin, 0)
+        cap_entries = rows * table.max_fanout if cap_entries is None else cap_entries
+        cap_wait = rows if cap_wait is None else cap_wait
+        cap_unsub = spans if cap_unsub is None else cap_unsub
+        cap_reply = 58 * rows + 12 * spans if cap_reply is None else cap_reply
+
+        def buf(n, dt=torch.int64):
+            return torch.empty(max(int(n), 1), dtype=dt, device=dev)
+
+        r = WriteRoute()
+        r.outcome = buf(n_rows, torch.uint8)
+        r.chan_off = torch.zeros(table.n_chans + 1, dtype=torch.int64, device=dev)
+        r.ent_id, r.ent_row = buf(cap_entries), buf(cap_entries)
+        r.wait_row, r.wait_id, r.wait_wid = buf(cap_wait), buf(cap_wait), buf(cap_wait)
+        r.unsub_id = buf(cap_unsub)
+        r.reply = buf(cap_reply, torch.uint8)
+        torch.cuda.synchronize(dev)  # (as Columns: the zero fill is done)
+        s = r.s
+        s.cap_rows, s.outcome = max(n_rows, 1), r.outcome.data_ptr()
+        s.disp = NxgDispatch(cap_entries, r.chan_off.data_ptr(), r.ent_id.data_ptr(),
+                             r.ent_row.data_ptr(), None, 0, 0)
+        s.cap_wait, s.wait_row, s.wait_id, s.wait_wid = (
+            cap_wait, r.wait_row.data_ptr(), r.wait_id.data_ptr(), r.wait_wid.data_ptr())
+        s.cap_unsub, s.unsub_id = cap_unsub, r.unsub_id.data_ptr()
+        s.cap_reply, s.reply = cap_reply, r.reply.data_ptr()
+        tb = table.c_struct()
+        if not hasattr(frame, "data_ptr") or frame.device.type != "cuda":
+            raise CodecError("frame: the device tensor the columns were decoded from")
+        ptr = frame.data_ptr()
+        err = NetidxError()
+        ok = lib().nxg_route_writes(self.ctx, C.byref(tb), C.c_void_p(ptr), C.byref(cols.s),
+                                    C.byref(wcols.s), row_begin, ctl_begin, fresh_wid,
+                                    C.byref(s), C.byref(err))
+        if not ok and err.msg and b"NXG_CAPACITY" in err.msg:
+            msg = err.msg.decode()
+            lib().nxg_error_free(C.byref(err))
+            raise RouteCapacity(msg, r)
+        _check(ok, err)
+        r.row_begin = row_begin
+        return r
+
     def decode_range(self, dframe, frame_len, begin, end, cols):
         """Decode the messages that start in [begin, end) of a device frame (rows at cols[0:]);
         returns the NxgRange summary (entry / exit / n_rows / ok)."""
@@ -1101,6 +1176,109 @@ class PubTable:
                            p(self.client), self.n_clients, p(self.cur_tag), p(self.cur_fixed),
                            p(self.cur_aux), p(self.cur_heap), p(self.cur_ctag),
                            p(self.cur_cfixed), p(self.cur_caux))
+
+
+NOT_SUBSCRIBED = 0xFFFFFFFF
+PERM_WRITE = 0x04  # Permissions::WRITE (resolver_server/auth.rs:26)
+WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED, WRITE_NOT_ACCEPTED = 0, 1, 2, 3
+
+
+class WriteTable:
+    """Device-resident state of one client for write routing (include/nxg_codec.h NxgWriteTable):
+    cl.subscribed as a dense Id -> Permissions table and pb.on_write as Id -> slot plus each slot's
+    open channels in list order (CSR), as write() reads them (publisher/server.rs:201-217)."""
+
+    def __init__(self, perm_of_id, slot_of_id, slot_chan_off, chan, n_chans, device="cuda"):
+        import torch
+
+        def t(a, dt):
+            return torch.as_tensor(np.array(a, dtype=dt, copy=True)).to(device)
+
+        self.perm_of_id = t(perm_of_id, np.uint32).view(torch.int32)
+        self.slot_of_id = t(slot_of_id, np.uint32).view(torch.int32)
+        offs = np.array(slot_chan_off, dtype=np.uint32)
+        self.slot_chan_off = t(offs, np.uint32).view(torch.int32)
+        self.chan = t(chan, np.uint32).view(torch.int32)
+        self.n_chans = int(n_chans)
+        self.n_slots = max(len(offs) - 1, 0)
+        self.max_fanout = int((offs[1:].astype(np.int64) - offs[:-1]).max()) if self.n_slots else 0
+        assert self.perm_of_id.numel() == self.slot_of_id.numel()
+
+    @classmethod
+    def from_state(cls, subscribed, on_write, n_chans, n_ids=None, device="cuda"):
+        """subscribed: {id: permission bits} (cl.subscribed); on_write: {id: [open chan, ...]}
+        (pb.on_write after the retain of server.rs:207-214). n_ids: the table's extent (default:
+        one past the largest Id of either map)."""
+        if n_ids is None:
+            n_ids = max([-1] + list(subscribed) + list(on_write)) + 1
+        perm = np.full(n_ids, NOT_SUBSCRIBED, np.uint32)
+        slot_of_id = np.full(n_ids, NO_SLOT, np.uint32)
+        for i, p in subscribed.items():
+            if i < n_ids:
+                perm[i] = p
+        offs, chans = [0], []
+        for slot, (i, cs) in enumerate(sorted(on_write.items())):
+            if i < n_ids:
+                slot_of_id[i] = slot
+            chans.extend(cs)
+            offs.append(len(chans))
+        return cls(perm, slot_of_id, offs, chans, n_chans, device)
+
+    def c_struct(self):
+        def p(x):
+            return x.data_ptr() if x.numel() else None
+        return NxgWriteTable(self.perm_of_id.numel(), p(self.perm_of_id), p(self.slot_of_id),
+                             self.n_slots, p(self.slot_chan_off), p(self.chan), self.n_chans)
+
+
+class WriteRoute:
+    """What Codec.route_writes returns (include/nxg_codec.h NxgWriteRoute): device tensors
+    outcome (per row of the columns), chan_off / ent_id / ent_row (per-channel requests, as
+    Dispatch), wait_row / wait_id / wait_wid, unsub_id and reply, with the counts in `s`."""
+
+    def __init__(self):
+        self.s = NxgWriteRoute()
+        self.row_begin = 0
+
+    def __getattr__(self, k):
+        s = self.__dict__.get("s")
+        if s is not None and k in ("n_entries", "n_wait", "n_unsub", "n_replies", "reply_len",
+                                   "n_fresh", "next_row", "next_ctl"):
+            return int(getattr(s, k))
+        raise AttributeError(k)
+
+    @property
+    def stopped_at_subscribe(self):
+        return bool(self.s.stopped_at_subscribe)
+
+    @property
+    def n_outcome(self):
+        return [int(x) for x in self.s.n_outcome]
+
+    def batches(self):
+        """{chan: [(id, row), ...]} on the host (non-empty channels only)."""
+        return Dispatch(self.chan_off, self.ent_id, self.ent_row, None, self.n_entries,
+                        0).batches()
+
+    def numpy(self):
+        """Host copies, trimmed: outcome of the processed rows [row_begin, next_row), the wait
+        triples, unsub_id and the reply bytes."""
+        u = lambda t, n: t[:n].cpu().numpy().view(np.uint64)
+        return {"outcome": self.outcome[self.row_begin:self.next_row].cpu().numpy(),
+                "wait": list(zip(u(self.wait_row, self.n_wait).tolist(),
+                                 u(self.wait_id, self.n_wait).tolist(),
+                                 u(self.wait_wid, self.n_wait).tolist())),
+                "unsub_id": u(self.unsub_id, self.n_unsub).tolist(),
+                "reply": self.reply[: self.reply_len].cpu().numpy().tobytes()}
+
+
+class RouteCapacity(CodecError):
+    """nxg_route_writes: a capacity was exceeded; `route` holds the required counts (n_entries,
+    n_wait, n_unsub, reply_len)."""
+
+    def __init__(self, msg, route):
+        super().__init__(msg)
+        self.route = route
 
 
 def _heap_ptr(heap):

@@ -124,6 +124,11 @@ struct NxgCtx {
     uint8_t* dwflags = nullptr;
     uint64_t* dwid = nullptr;
     size_t dw_cap = 0;
+    // write routing (nxg_route_writes.hip): the first Unsubscribe row per Id, tagged with the
+    // call's epoch (24 bits; the table is cleared when it is grown and when the epoch wraps)
+    uint64_t* rw_first = nullptr;
+    size_t rw_first_cap = 0;
+    uint32_t rw_epoch = 0;
     // in-flight async operations (completed in order by nxg_ctx_sync)
     struct Pending {
         int kind;  // 1 decode, 2 encode
@@ -925,6 +930,7 @@ void nxg_ctx_destroy(NxgCtx* c) {
     if (c->aw_host) (void)hipHostFree(c->aw_host);
     if (c->dwflags) (void)hipFree(c->dwflags);
     if (c->dwid) (void)hipFree(c->dwid);
+    if (c->rw_first) (void)hipFree(c->rw_first);
     if (c->dst) (void)hipFree(c->dst);
     if (c->hst) (void)hipHostFree(c->hst);
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -2687,6 +2693,161 @@ bool nxg_encode_writes(NxgCtx* c, const NxgColumns* in, const NxgWriteCols* win,
                        NetidxError* err) {
     if (!writes_args_ok(c, in, win, err)) return false;
     return encode_impl(c, in, heap, out, cap, len_out, err, win);
+}
+
+// ---- write routing (publisher/server.rs:171-245, 497-576) ---------------------------------------
+// Replaces handle_batch_inner's Write and Unsubscribe arms: nxg_route_writes.hip's passes, the
+// dispatch of nxg_dispatch.hip for the channel fan-out, one copy of the head, one synchronisation.
+bool nxg_route_writes(NxgCtx* c, const NxgWriteTable* tab, const uint8_t* frame,
+                      const NxgColumns* cols, const NxgWriteCols* wcols, uint64_t row_begin,
+                      uint64_t ctl_begin, uint64_t fresh_wid, NxgWriteRoute* out, NetidxError* err) {
+    // (the argument checks come before any use of the context)
+    if (!c || !tab || !cols || !out) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!wcols) {
+        set_err(err, "wcols is null: the rows' wflags / wid come from nxg_decode_writes");
+        return false;
+    }
+    if (cols->mem != NXG_MEM_DEVICE || wcols->mem != NXG_MEM_DEVICE) {
+        set_err(err, "cols->mem / wcols->mem: write routing takes device columns");
+        return false;
+    }
+    if (cols->layout != NXG_LAYOUT_MIXED || !mixed_capable(cols) || !cols->id) {
+        set_err(err, "cols->layout: write batches are MIXED-layout columns");
+        return false;
+    }
+    const uint64_t n_rows = cols->n_rows, n_ctl = cols->n_ctl;
+    if (row_begin > n_rows) {
+        set_err(err, "row_begin %llu is past the batch's %llu rows", (unsigned long long)row_begin,
+                (unsigned long long)n_rows);
+        return false;
+    }
+    if (ctl_begin > n_ctl) {
+        set_err(err, "ctl_begin %llu is past the batch's %llu control spans",
+                (unsigned long long)ctl_begin, (unsigned long long)n_ctl);
+        return false;
+    }
+    const uint64_t rows = n_rows - row_begin, spans = n_ctl - ctl_begin;
+    if (rows >= 0xffffffffull) {
+        set_err(err, "row_begin: a call covers fewer than 2^32 rows");
+        return false;
+    }
+    if (n_rows && (!wcols->wflags || !wcols->wid || wcols->cap_rows < n_rows)) {
+        set_err(err, "wcols holds %llu rows, the batch %llu", (unsigned long long)wcols->cap_rows,
+                (unsigned long long)n_rows);
+        return false;
+    }
+    if (spans && !frame) {
+        set_err(err, "frame is null: the Unsubscribe spans' Ids are read from it");
+        return false;
+    }
+    if ((tab->n_ids && (!tab->perm_of_id || !tab->slot_of_id)) ||
+        (tab->n_slots && !tab->slot_chan_off)) {  // (chan may be null: every list empty)
+        set_err(err, "tab: null table array");
+        return false;
+    }
+    if (out->cap_rows < n_rows || (n_rows && !out->outcome)) {
+        set_err(err, "out->cap_rows: outcome[] holds %llu rows, the batch %llu",
+                (unsigned long long)out->cap_rows, (unsigned long long)n_rows);
+        return false;
+    }
+    if (!out->disp.chan_off || (out->disp.cap_entries && (!out->disp.ent_sub || !out->disp.ent_row)) ||
+        (out->cap_wait && (!out->wait_row || !out->wait_id || !out->wait_wid)) ||
+        (out->cap_unsub && !out->unsub_id) || (out->cap_reply && !out->reply)) {
+        set_err(err, "out: null output array");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // the first-unsubscribe table: grown (and cleared) on demand, never cleared per call
+    if (tab->n_ids > c->rw_first_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->rw_first) HIPCHK(hipFree(c->rw_first));
+        c->rw_first = nullptr;
+        c->rw_first_cap = 0;
+        const size_t n = std::max<size_t>(tab->n_ids, 4096);
+        HIPCHK(hipMalloc(&c->rw_first, n * 8));
+        HIPCHK(hipMemsetAsync(c->rw_first, 0, n * 8, c->stream));
+        c->rw_first_cap = n;
+    }
+    if (++c->rw_epoch >= (1u << 24)) {  // wrap: stale words could alias epoch 1 again
+        c->rw_epoch = 1;
+        if (c->rw_first) HIPCHK(hipMemsetAsync(c->rw_first, 0, c->rw_first_cap * 8, c->stream));
+    }
+    const size_t rw = (nxg_rw_scratch_bytes(rows, spans) + 255) & ~size_t(255);
+    const size_t last = (tab->n_slots * 8 + 255) & ~size_t(255);
+    const size_t need = rw + last + 64 + nxg_disp_scratch_bytes(rows, tab->n_chans);
+    if (need > c->dscratch_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
+        c->dscratch = nullptr;
+        const size_t sz = std::max(need, c->dscratch_cap * 2);
+        c->dscratch_cap = 0;
+        HIPCHK(hipMalloc(&c->dscratch, sz));
+        c->dscratch_cap = sz;
+    }
+    NxgRwArgs a{};
+    a.tab = *tab;
+    a.frame = frame;
+    a.id = cols->id;
+    a.wflags = wcols->wflags;
+    a.wid = wcols->wid;
+    a.ctl_row = cols->ctl_row;
+    a.ctl_off = cols->ctl_off;
+    a.ctl_len = cols->ctl_len;
+    a.ctl_variant = cols->ctl_variant;
+    a.n_rows = n_rows;
+    a.n_ctl = n_ctl;
+    a.row_begin = row_begin;
+    a.ctl_begin = ctl_begin;
+    a.fresh_wid = fresh_wid;
+    a.first_unsub = c->rw_first;
+    a.epoch = c->rw_epoch;
+    a.outcome = out->outcome;
+    a.wait_row = out->wait_row;
+    a.wait_id = out->wait_id;
+    a.wait_wid = out->wait_wid;
+    a.cap_wait = out->cap_wait;
+    a.unsub_id = out->unsub_id;
+    a.cap_unsub = out->cap_unsub;
+    a.reply = out->reply;
+    a.cap_reply = out->cap_reply;
+    HIPCHK(nxg_launch_route_writes(a, c->dscratch, c->dscratch + rw + last, out->disp.chan_off,
+                                   out->disp.ent_sub, out->disp.ent_row, out->disp.cap_entries,
+                                   reinterpret_cast<uint64_t*>(c->dscratch + rw), c->ncu,
+                                   c->stream));
+    NxgRwHead h;
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const uint64_t s = h.first_sub_inv ? ~h.first_sub_inv : n_ctl;
+    out->n_entries = out->disp.n_entries = h.n_entries;
+    out->disp.n_unmatched = 0;
+    out->n_wait = h.n_wait;
+    out->n_unsub = s - ctl_begin;
+    out->n_replies = h.n_row_replies + out->n_unsub;
+    out->reply_len = h.row_bytes + h.span_bytes;
+    out->n_fresh = h.n_fresh;
+    for (int o = 0; o < 4; o++) out->n_outcome[o] = h.n_outcome[o];
+    out->next_row = h.next_row;
+    out->next_ctl = h.next_ctl;
+    out->stopped_at_subscribe = s < n_ctl ? 1u : 0u;
+    out->pad = 0;
+    if (h.n_entries > out->disp.cap_entries || h.n_wait > out->cap_wait ||
+        out->n_unsub > out->cap_unsub || out->reply_len > out->cap_reply) {
+        set_err(err, "write routing needs %llu entries, %llu wait-list rows, %llu unsubscribed ids, "
+                     "%llu reply bytes; capacities are %llu, %llu, %llu, %llu (NXG_CAPACITY)",
+                (unsigned long long)h.n_entries, (unsigned long long)h.n_wait,
+                (unsigned long long)out->n_unsub, (unsigned long long)out->reply_len,
+                (unsigned long long)out->disp.cap_entries, (unsigned long long)out->cap_wait,
+                (unsigned long long)out->cap_unsub, (unsigned long long)out->cap_reply);
+        return false;
+    }
+    return true;
 }
 
 bool nxg_encode_updates_async(NxgCtx* c, const NxgColumns* din, const uint8_t* dheap,

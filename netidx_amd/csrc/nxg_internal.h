@@ -231,6 +231,62 @@ hipError_t nxg_launch_pub_stage2(const NxgPubTable& tb, const NxgPubBatch& b, ui
 hipError_t nxg_launch_pub_deep(const NxgPubTable& tb, const NxgPubBatch& b, uint8_t* scratch,
                                const uint32_t* prev_used, int ncu, hipStream_t s);
 const uint32_t* nxg_pub_prev(uint8_t* scratch, uint64_t n, uint64_t n_slots);
+// write routing (nxg_route_writes.hip): the call's head (device, zeroed per call, copied back
+// whole after the last launch) and the arguments every kernel of the call takes by value
+struct NxgRwHead {
+    uint64_t first_sub_inv;  // ~k of the first Subscribe span k >= ctl_begin (atomicMax; 0: none)
+    uint64_t n_fresh, n_wait;
+    uint64_t span_bytes, row_bytes;  // reply bytes of the Unsubscribe spans / of the rows
+    uint64_t n_row_replies;
+    uint64_t n_outcome[4];
+    uint64_t n_entries, next_row, next_ctl;
+    uint64_t pad[3];
+};
+static_assert(sizeof(NxgRwHead) == 128, "NxgRwHead layout");
+constexpr int kRwBlock = 256;  // rows (and spans) per workgroup of the scans
+struct NxgRwArgs {
+    NxgWriteTable tab;
+    const uint8_t* frame;
+    const uint64_t* id;  // the decoded columns
+    const uint8_t* wflags;
+    const uint64_t* wid;
+    const uint64_t* ctl_row;
+    const uint64_t* ctl_off;
+    const uint32_t* ctl_len;
+    const uint8_t* ctl_variant;
+    uint64_t n_rows, n_ctl, row_begin, ctl_begin, fresh_wid;
+    uint64_t* first_unsub;  // [>= n_ids] ctx-owned: epoch << 40 | ~(the Id's first Unsubscribe row)
+    uint32_t epoch;
+    // outputs
+    uint8_t* outcome;
+    uint64_t* wait_row;
+    uint64_t* wait_id;
+    uint64_t* wait_wid;
+    uint64_t cap_wait;
+    uint64_t* unsub_id;
+    uint64_t cap_unsub;
+    uint8_t* reply;
+    uint64_t cap_reply;
+    // scratch, placed by the launcher
+    NxgRwHead* head;
+    uint64_t* cblk;  // per row block: (rows without a WriteId, rows on the wait list), packed
+    uint64_t* oblk;  // per row block: rows of outcome (0, 1), then of (2, 3), packed likewise
+    uint64_t* zblk;  // per row block: reply bytes
+    uint64_t* nblk;  // per row block: replies
+    uint64_t* sblk;  // per span block: reply bytes
+    uint64_t* uid;   // per span: the Unsubscribe's Id
+    uint32_t* rloc;  // per row / span: reply bytes before it within its block
+    uint32_t* sloc;
+    uint8_t* mode;   // per row from row_begin: the dispatch's row_mode
+};
+// `scratch` holds nxg_rw_scratch_bytes(rows from row_begin, spans from ctl_begin) bytes,
+// `disp_scratch` 64 + nxg_disp_scratch_bytes(those rows, n_chans); neither needs initialising.
+// `last_row`: n_slots words for the dispatch. a.head is at `scratch` afterwards.
+uint64_t nxg_rw_scratch_bytes(uint64_t rows, uint64_t spans);
+hipError_t nxg_launch_route_writes(NxgRwArgs a, uint8_t* scratch, uint8_t* disp_scratch,
+                                   uint64_t* chan_off, uint64_t* ent_sub, uint64_t* ent_row,
+                                   uint64_t cap_entries, uint64_t* last_row, int ncu,
+                                   hipStream_t s);
 // exclusive sums of M u32 counts into u64 offsets (nxg_publish.hip); bsum: M / 4096 + 2 words
 hipError_t nxg_scan_u32(const uint32_t* hist, uint64_t M, uint64_t* off, uint64_t* bsum,
                         hipStream_t s);
