@@ -139,7 +139,14 @@ void nxg_columns_free(NxgCtx* ctx, NxgColumns* cols);
  * `frame` is one frame payload (no u32 header; channel.rs:379-443 strips it), host or device
  * memory. `out` must come from nxg_columns_alloc. Synchronous. Returns false only on API
  * misuse or a HIP failure. A malformed frame returns true with st->err_kind != 0, and the whole
- * frame is rejected, as in connection.rs:228-231. */
+ * frame is rejected, as in connection.rs:228-231.
+ * A well-formed frame that needs more rows, children or control spans than out->cap_rows,
+ * cap_children or cap_ctl returns true with st->err_kind = NXG_CAPACITY (its err_offset is
+ * unspecified). No element at or past any capacity of any array is written, whatever the outcome.
+ * After NXG_CAPACITY n_rows, n_children and n_ctl (in *st and in *out) are what the frame needs,
+ * so columns of those sizes take it; what the arrays hold below the capacities is unspecified. A
+ * format error takes precedence over NXG_CAPACITY. The same holds for the async forms below, whose
+ * status nxg_ctx_sync fills; in a backlog the other frames' columns are decoded as usual. */
 bool nxg_decode_updates(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColumns* out,
                         uint32_t flags, NxgStatus* st, NetidxError* err);
 /* Asynchronous device-resident variant: enqueue on the ctx stream; no host sync. Only the
@@ -179,7 +186,8 @@ bool nxg_decode_frames_async(NxgCtx* ctx, uint32_t n, const uint8_t* const* dfra
 /* ---- encode: replaces handle_updates' queue_send loop (server.rs:610-612) ----------------
  * `heap` holds the bytes that string/bytes/decimal/abstract offsets and ctl spans refer to.
  * It may be NULL for pure fixed-width columns. in/heap/out must all be device memory, or all
- * host memory. */
+ * host memory. An encode that fails (a buffer too small) may leave any bytes inside
+ * [out, out + cap); failing or not, it writes nothing outside. */
 bool nxg_encoded_len(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, uint64_t* len_out,
                      NetidxError* err);
 bool nxg_encode_updates(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap, uint8_t* out,
@@ -254,7 +262,9 @@ bool nxg_decode_writes(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColum
  * copied from `heap` before row ctl_row[k]. in/win/heap/out all device memory, or all host memory.
  * out NULL: the length only. A message longer than MAX_BATCH fails with TooBig. A batch whose total exceeds MAX_BATCH
  * (0x3FFFFFFF bytes) is refused before anything is written: size it with nxg_encoded_writes_len
- * and split the rows; the frame cut of nxg_encode_frames is not extended to write batches. */
+ * and split the rows; the frame cut of nxg_encode_frames is not extended to write batches. A failed
+ * encode (a buffer too small) may leave any bytes inside [out, out + cap); failing or not, it
+ * writes nothing outside. */
 bool nxg_encoded_writes_len(NxgCtx* ctx, const NxgColumns* in, const NxgWriteCols* win,
                             const uint8_t* heap, uint64_t* len_out, NetidxError* err);
 bool nxg_encode_writes(NxgCtx* ctx, const NxgColumns* in, const NxgWriteCols* win,
@@ -597,7 +607,9 @@ bool nxg_publish_unsubscribes(NxgCtx* ctx, const uint64_t* id, const uint32_t* c
  * decoder). *consumed = the batch's length in bytes.
  * Deviation: Event::decode on an empty buffer panics in the reference; here it is
  * NXG_BUFFER_SHORT. Synchronous; false on misuse or a HIP failure. A decode error is reported in
- * `status` (as nxg_decode_updates does), with n_rows = n_children = 0. */
+ * `status` (as nxg_decode_updates does), with n_rows = n_children = 0. A batch that needs more
+ * rows or children than out->cap_rows / cap_children is NXG_CAPACITY there, and no element at or
+ * past a capacity of any array is written, whatever the outcome. */
 #define NXG_TAG_UNSUBSCRIBED 0x40
 #define NXG_PATH_ARCHIVE 3
 #define NXG_PATH_ARCHIVE_FAST 5
@@ -607,7 +619,9 @@ bool nxg_decode_archive_batch(NxgCtx* ctx, const uint8_t* buf, uint64_t len, Nxg
  * device MIXED-layout columns in the same form (id = the u32 Id, tag NXG_TAG_UNSUBSCRIBED for
  * Event::Unsubscribed; text at heap + fixed, device memory; no control messages) to `out`
  * (device memory, `cap` bytes; NULL: *len_out = the length only). Synchronous. TooBig when
- * count * size_of::<BatchItem>() exceeds MAX_VEC or a value violates a size guard. */
+ * count * size_of::<BatchItem>() exceeds MAX_VEC or a value violates a size guard. A failed encode
+ * (a buffer too small) may leave any bytes inside [out, out + cap); failing or not, it writes
+ * nothing outside. */
 bool nxg_encode_archive_batch(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap,
                               uint8_t* out, uint64_t cap, uint64_t* len_out, NetidxError* err);
 

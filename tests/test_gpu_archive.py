@@ -14,6 +14,7 @@ import zlib
 import numpy as np
 import pytest
 
+import guards
 import nxo
 
 pytestmark = pytest.mark.gpu
@@ -33,22 +34,29 @@ def codec():
     c.close()
 
 
-def gpu_decode(codec, buf, cap_rows=None, cap_children=None):
+def gpu_decode(codec, buf, cap_rows=None, cap_children=None, spare=None):
+    """spare: the columns carry a band of that many sentinel elements behind each capacity
+    (tests/guards.py), checked after the decode."""
     import torch
     import netidx_amd
     from netidx_amd.codec import Columns
     buf = np.frombuffer(bytes(buf), np.uint8) if not isinstance(buf, np.ndarray) else buf
     n = len(buf)
     d = torch.from_numpy(buf.copy()).cuda() if n else torch.zeros(1, dtype=torch.uint8).cuda()
-    cols = Columns(cap_rows if cap_rows is not None else n // 2 + 1,
-                   cap_children if cap_children is not None else n + 1, 1,
-                   netidx_amd.LAYOUT_MIXED, "cuda")
+    caps = (cap_rows if cap_rows is not None else n // 2 + 1,
+            cap_children if cap_children is not None else n + 1, 1)
+    if spare:
+        cols = guards.guarded_columns(*caps, netidx_amd.LAYOUT_MIXED, "cuda", spare)
+    else:
+        cols = Columns(*caps, netidx_amd.LAYOUT_MIXED, "cuda")
     st, used = codec.decode_archive(d, n, cols, check=False)
+    if spare:
+        guards.assert_guards(cols)
     return cols, st, used
 
 
-def assert_matches_oracle(codec, buf, **caps):
-    cols, st, used = gpu_decode(codec, buf, **caps)
+def assert_matches_oracle(codec, buf, spare=None, **caps):
+    cols, st, used = gpu_decode(codec, buf, spare=spare, **caps)
     d, r = nxo.decode_archive(buf, caps.get("cap_rows"), caps.get("cap_children"))
     o = d.trim()
     assert (st.err_kind, st.err_offset) == (o["err_kind"], o["err_offset"])
@@ -193,9 +201,10 @@ def test_archive_errors_deep_in_the_batch(codec):
 def test_archive_capacity(codec):
     from netidx_amd import synth
     buf = archive_bytes(synth.archive_columns(10_000, seed=12))
-    st = assert_matches_oracle(codec, buf, cap_rows=5000)
+    # (a band as long as the batch's rows: whatever a decoder wrote behind the 5000th row is seen)
+    st = assert_matches_oracle(codec, buf, spare=10_512, cap_rows=5000)
     assert st.err_kind == 7
-    cols, st, used = gpu_decode(codec, buf, cap_rows=10_000)
+    cols, st, used = gpu_decode(codec, buf, cap_rows=10_000, spare=10_512)
     assert st.err_kind == 0 and st.n_rows == 10_000
 
 
