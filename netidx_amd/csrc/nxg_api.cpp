@@ -89,6 +89,12 @@ struct NxgCtx {
     // skipped for the next kSeqSkipCalls calls (NXG_F64_PATH=run skips it always)
     uint32_t seq_left = 0;
     bool no_seq = false;
+    // a backlog of such frames (nxg_decode_frames_async): grouped into launches of the backlog
+    // kernel on a grid of seq_group_wgs resident workgroups (NXG_F64S_GROUP=0: one launch per
+    // frame; NXG_F64S_GROUP_WGS=n caps the grid, tests)
+    bool seq_group = true;
+    int seq_group_wgs = 0;
+    uint32_t bl_launches = 0, bl_frames = 0;  // decode launches / frames of the last backlog call
     // the sequential-id f64 encoder (nxg_encode_f64_seq.hip): after it declines a batch (ids not
     // counting up by one) it is skipped for the next kSeqSkipCalls f64 encodes; NXG_F64_ENC=tile
     // skips it always
@@ -774,6 +780,74 @@ bool covered(const std::vector<Span>& by, const std::vector<Span>& a) {
     return true;
 }
 
+// ---- a backlog of sequential-id frames, grouped into launches (nxg_f64s_backlog_kernel) ---------
+struct SeqPlan {
+    uint8_t start;   // a launch starts in front of this frame
+    uint8_t reuse;   // it writes the columns of an earlier frame of its launch (kF64sReuse)
+    uint32_t tiles;  // its tiles per wave on `waves` waves (0: not a frame for the backlog kernel)
+};
+
+// Which frames of a backlog share a launch; returns the number of launches. Pure: addresses and
+// lengths only. The waves of one launch run the frames in backlog order, but no wave waits for
+// another, so inside a launch no frame may read or write memory that another one writes. One case
+// is exempt: frames with the same id and fixed arrays, the same cap_rows and the same length.
+// There every row is written by the same wave for both frames (the wave of a row follows from
+// the grid, and the rounds a wave makes from the length), and that wave takes them in order
+// (kF64sReuse). A launch is cut in front of
+// frame j when
+//   - frame j is empty, or too long for the backlog kernel (it goes alone, and so ends its launch);
+//   - the launch holds kF64sBacklogMax frames;
+//   - frame j's bytes overlap the columns of an earlier frame of the launch, or its columns the
+//     bytes of one (per-frame launches would run the one wholly before the other);
+//   - its columns overlap an earlier frame's otherwise than in the exempt case.
+uint32_t plan_seq_backlog(uint32_t n, const uint8_t* const* frames, const uint64_t* lens,
+                          const NxgColumns* const* cols, uint32_t waves, SeqPlan* out) {
+    std::vector<Span> sp;         // the column spans of the launch's frames, frame after frame
+    std::vector<size_t> first;    // frame g0 + i of the launch: sp[first[i], first[i + 1])
+    std::vector<Span> mine;
+    uint32_t g0 = 0, launches = 0;
+    bool open = false;  // the launch takes more frames
+    auto hit = [](const Span* a, const Span* ae, const Span* b, const Span* be) {
+        for (; a != ae; a++)
+            for (const Span* y = b; y != be; y++)
+                if (a->lo < y->hi && y->lo < a->hi) return true;
+        return false;
+    };
+    for (uint32_t j = 0; j < n; j++) {
+        const bool takes = nxg_f64s_backlog_takes(lens[j]);
+        out[j].tiles = takes ? nxg_f64s_tiles_per_wave(lens[j], waves) : 0u;
+        mine.clear();
+        cols_spans(cols[j], &mine);
+        const Span wj = span_of(frames[j], lens[j]);
+        bool cut = !open || !takes || j - g0 >= kF64sBacklogMax, reuse = false;
+        for (uint32_t i = g0; i < j && !cut; i++) {
+            const Span *si = sp.data() + first[i - g0], *se = sp.data() + first[i - g0 + 1];
+            const Span wi = span_of(frames[i], lens[i]);
+            const Span *mb = mine.data(), *me = mb + mine.size();
+            if (hit(&wj, &wj + 1, si, se) || hit(mb, me, &wi, &wi + 1)) {
+                cut = true;
+            } else if (cols[i]->id == cols[j]->id && cols[i]->fixed == cols[j]->fixed &&
+                       cols[i]->cap_rows == cols[j]->cap_rows && lens[i] == lens[j]) {
+                reuse = true;
+            } else if (hit(mb, me, si, se)) {
+                cut = true;
+            }
+        }
+        if (cut) {
+            sp.clear();
+            first.assign(1, 0);
+            g0 = j;
+            open = takes;
+            if (lens[j] > 0) launches++;
+        }
+        out[j].start = cut;
+        out[j].reuse = !cut && reuse;
+        sp.insert(sp.end(), mine.begin(), mine.end());
+        first.push_back(sp.size());
+    }
+    return launches;
+}
+
 // a pending decode done again from the start, synchronously (its first attempt's columns were
 // overwritten by an earlier frame's late fallback)
 bool redo_decode(NxgCtx* c, const NxgCtx::Pending& p, NxgStatus* s, NetidxError* err) {
@@ -821,6 +895,45 @@ void nxg_debug_status(NxgCtx* c, unsigned long long out[6]) {
 unsigned nxg_debug_enc_kernel(NxgCtx* c) { return c ? c->last_enc_kernel : 0u; }
 void nxg_debug_diag(NxgCtx* c, unsigned long long out[8]) {
     for (int i = 0; i < 8; i++) out[i] = c ? c->last.diag[i] : 0;
+}
+// Not part of the ABI: the last nxg_decode_frames_async call that the sequential-id decoder took:
+// its decode launches, its frames, the backlog kernel's grid (workgroups), grouping on (1) or off.
+void nxg_debug_backlog(NxgCtx* c, unsigned long long out[4]) {
+    out[0] = c ? c->bl_launches : 0;
+    out[1] = c ? c->bl_frames : 0;
+    out[2] = c ? (unsigned long long)c->seq_group_wgs : 0;
+    out[3] = c ? c->seq_group : 0;
+}
+// Not part of the ABI, and needs no GPU: the grouping plan of a backlog of n frames at addresses
+// wire[j], lens[j] bytes long, into F64 columns id[j], fixed[j] of cap_rows[j] rows, for a grid of
+// `waves` waves. start[j]: a launch starts in front of frame j; reuse[j]: the frame writes the
+// columns of an earlier frame of its launch; tiles[j]: its tiles per wave (0: it goes alone, on
+// the per-frame kernel, or is empty). Returns the number of launches.
+uint32_t nxg_debug_f64s_plan(uint32_t n, const uint64_t* wire, const uint64_t* lens,
+                             const uint64_t* id, const uint64_t* fixed, const uint64_t* cap_rows,
+                             uint32_t waves, uint8_t* start, uint8_t* reuse, uint32_t* tiles) {
+    std::vector<NxgColumns> cs(n);
+    std::vector<const NxgColumns*> cp(n);
+    std::vector<const uint8_t*> fp(n);
+    std::vector<SeqPlan> plan(n);
+    for (uint32_t j = 0; j < n; j++) {
+        memset(&cs[j], 0, sizeof(NxgColumns));
+        cs[j].layout = NXG_LAYOUT_F64;
+        cs[j].mem = NXG_MEM_DEVICE;
+        cs[j].id = (uint64_t*)(uintptr_t)id[j];
+        cs[j].fixed = (uint64_t*)(uintptr_t)fixed[j];
+        cs[j].cap_rows = cap_rows[j];
+        cp[j] = &cs[j];
+        fp[j] = (const uint8_t*)(uintptr_t)wire[j];
+    }
+    const uint32_t launches =
+        plan_seq_backlog(n, fp.data(), lens, cp.data(), waves ? waves : 1u, plan.data());
+    for (uint32_t j = 0; j < n; j++) {
+        start[j] = plan[j].start;
+        reuse[j] = plan[j].reuse;
+        tiles[j] = plan[j].tiles;
+    }
+    return launches;
 }
 
 // Not part of the ABI: the last fast archive attempt's FaHead (fast_fail | arrived << 32, end,
@@ -885,6 +998,12 @@ NxgCtx* nxg_ctx_new(int device, NetidxError* err) {
     const char* fp = getenv("NXG_F64_PATH");
     c->force_x = fp && strcmp(fp, "x") == 0;
     c->no_seq = fp && (strcmp(fp, "run") == 0 || strcmp(fp, "x") == 0);
+    const char* sg = getenv("NXG_F64S_GROUP");
+    c->seq_group = !(sg && sg[0] == '0');
+    c->seq_group_wgs = nxg_f64s_backlog_wgs(c->ncu);
+    const char* sw = getenv("NXG_F64S_GROUP_WGS");
+    if (sw && strtol(sw, nullptr, 0) > 0)
+        c->seq_group_wgs = (int)std::min<long>(c->seq_group_wgs, strtol(sw, nullptr, 0));
     const char* fe = getenv("NXG_F64_ENC");
     c->no_enc_seq = fe && strcmp(fe, "tile") == 0;
     const char* mp = getenv("NXG_MIXED_PATH");
@@ -1065,6 +1184,60 @@ bool nxg_decode_updates_async(NxgCtx* c, const uint8_t* dframe, uint64_t len, Nx
 
 namespace {
 
+// A backlog the sequential-id decoder takes, in as few launches as plan_seq_backlog allows.
+// Bookkeeping as on the length-run path below: one call per frame, with its own status slot and
+// zero-ahead slot; the frames of a launch become pending only once it is enqueued. A frame that
+// makes a launch of its own takes the per-frame kernel.
+bool decode_seq_backlog(NxgCtx* c, uint32_t n, const uint8_t* const* dframes, const uint64_t* lens,
+                        NxgColumns* const* douts, uint32_t flags, NetidxError* err) {
+    if (!set_device(c, err)) return false;
+    std::vector<SeqPlan> plan(n);
+    plan_seq_backlog(n, dframes, lens, douts, 4u * (uint32_t)c->seq_group_wgs, plan.data());
+    NxgF64sBacklog b;
+    b.n = 0;
+    b.pad = 0;
+    std::vector<NxgCtx::Pending> pend;
+    pend.reserve(std::min<uint32_t>(n, kF64sBacklogMax));
+    for (uint32_t j = 0; j < n; j++) {
+        const bool last = j + 1 == n || plan[j + 1].start;
+        DevStatus* st;
+        uint32_t slot;
+        if (!begin_call(c, &st, &slot, err)) return false;
+        DevStatus* zst = nxg_take_zero_slot();
+        pend.push_back({1, FAST_SEQ, dframes[j], lens[j], douts[j], nullptr, 0, st, slot, flags});
+        pend.back().seq = c->calls - 1;
+        if (lens[j] == 0) {
+            // an empty frame launches nothing: its zero-ahead slot is cleared here
+            HIPCHK(hipMemsetAsync(zst, 0, sizeof(DevStatus), c->stream));
+        } else if (plan[j].start && last) {
+            HIPCHK(nxg_launch_dec_f64s(dframes[j], lens[j], douts[j]->id, douts[j]->fixed,
+                                       douts[j]->cap_rows, st, zst, c->stream));
+            c->bl_launches++;
+        } else {
+            NxgF64sFrame& f = b.f[b.n++];
+            f.wire = dframes[j];
+            f.W = lens[j];
+            f.oid = douts[j]->id;
+            f.oval = douts[j]->fixed;
+            f.cap = douts[j]->cap_rows;
+            f.st = st;
+            f.zst = zst;
+            f.tiles_per_wave = plan[j].tiles;
+            f.flags = plan[j].reuse ? kF64sReuse : 0u;
+            if (last) {
+                HIPCHK(nxg_launch_dec_f64s_backlog(b, c->seq_group_wgs, c->stream));
+                c->bl_launches++;
+                b.n = 0;
+            }
+        }
+        if (last) {
+            c->pending.insert(c->pending.end(), pend.begin(), pend.end());
+            pend.clear();
+        }
+    }
+    return gather_pending(c, err);
+}
+
 bool decode_frames_async_impl(NxgCtx* c, uint32_t n, const uint8_t* const* dframes,
                               const uint64_t* lens, NxgColumns* const* douts, uint32_t flags,
                               NetidxError* err) {
@@ -1083,6 +1256,12 @@ bool decode_frames_async_impl(NxgCtx* c, uint32_t n, const uint8_t* const* dfram
             return false;
         }
         max_len = std::max(max_len, lens[j]);
+    }
+    if (!(flags & NXG_DECODE_HINT_MIXED) && seq_active(c)) {
+        c->bl_frames = n;
+        c->bl_launches = 0;
+        if (c->seq_group && n > 1) return decode_seq_backlog(c, n, dframes, lens, douts, flags, err);
+        for (uint32_t j = 0; j < n; j++) c->bl_launches += lens[j] > 0;
     }
     const bool run_path = !(flags & NXG_DECODE_HINT_MIXED) && !c->force_x &&
                           c->irregular_left == 0 && n > 1 && !seq_active(c);

@@ -49,6 +49,9 @@ inline int r_for(uint64_t W) { return W >= kXcdMin ? NXG_F64S_R : NXG_F64S_R_SMA
 #ifndef NXG_F64S_LDS
 #define NXG_F64S_LDS 0  // dynamic LDS per workgroup (A/B: caps the waves per CU)
 #endif
+#ifndef NXG_F64S_BL_STRIDE
+#define NXG_F64S_BL_STRIDE 1  // backlog kernel: wave gw's i-th tile is gw + i waves (0: gw K + i)
+#endif
 constexpr uint32_t F_XCD = 1;
 #ifndef NXG_F64S_XRUN
 #define NXG_F64S_XRUN 64  // workgroups per XCD run (frames past the Infinity Cache)
@@ -362,8 +365,68 @@ NXG_DEV bool emit_full_pairs_uniform(const uint8_t* __restrict__ wire, uint64_t 
     return bad != 0;
 }
 
+// One tile: the WREC records from k0, record k0 at byte p0 < W of a frame whose first id is i0.
+// Wave-uniform up to the loads: the width change inside the tile, then one of the three bodies
+// (one id width, a width change, the frame's end), the frame's status and the `bad` / `over` bits.
+template <int R>
+NXG_DEV void decode_tile(const uint8_t* __restrict__ wire, uint64_t W, uint64_t* __restrict__ oid,
+                         uint64_t* __restrict__ oval, uint64_t cap, DevStatus* __restrict__ st,
+                         uint64_t i0, uint64_t k0, uint64_t p0, uint32_t lane) {
+    using namespace f64rec16;
+    constexpr uint32_t WREC = 64 * R;  // records per wave
+    const uint64_t id0 = i0 + k0;
+    const uint32_t b = vl64(id0);
+    const uint64_t nxt = 1ull << (7 * b);  // the next width change (ids < 2^35: b <= 5)
+    const uint32_t L = 11u + b;
+    const uint32_t ks = nxt - id0 < WREC ? (uint32_t)(nxt - id0) : WREC;
+    const uint64_t pend = p0 + (uint64_t)ks * L + (uint64_t)(WREC - ks) * (L + 1);  // pos(k0 + WREC)
+    bool over = false, bad = b > 5;
+    if (!bad && pend + 48 <= W) {
+        // (ks == WREC: one id width in the whole wave -- all but at most four waves of a frame)
+        if (NXG_F64S_PAIR && NXG_F64S_UNIFORM && ks == WREC)
+            bad = emit_full_pairs_uniform<R>(wire, p0, L, k0, i0, oid, oval, cap, lane, over);
+        else
+            bad = NXG_F64S_PAIR
+                      ? emit_full_pairs<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over)
+                      : emit_full<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over);
+    } else if (!bad) {
+        // near the frame's end: n = #{k < WREC : pos(k0 + k) < W} (pos increases by 12..16 per
+        // record); the frame's last record must end exactly at W
+        uint32_t n = WREC;
+        if (pend > W) {
+            uint32_t lo = 0, hi = WREC;  // pos(k0 + lo) < W <= pos(k0 + hi)
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) / 2;
+                if (pos_of(i0, k0 + mid) < W) lo = mid;
+                else hi = mid;
+            }
+            n = hi;
+        }
+        const uint64_t pn = pos_of(i0, k0 + n);
+        if (pn == W && lane == 0) {  // this wave holds the frame's last record
+            st->n_rows = k0 + n;
+            st->path = 1;
+            st->diag[1] = 1;  // decoded by the sequential-id kernel (diagnostics)
+        }
+        if (pn < W && n < WREC) bad = true;  // (cannot happen: pos(k0 + n) >= W by the search)
+        else if (pn > W) bad = true;         // the frame does not end at a record boundary
+        else bad = emit_edge(wire, W, p0, L, ks, n, k0, i0, oid, oval, cap, lane, over);
+    }
+    if (__any(bad) && lane == 0) {
+        atomicOr(&st->irregular, 4u);  // ids do not count up by one: the length-run decoder
+        atomicOr(&st->fast_fail, 1u);
+    }
+    if (__any(over) && lane == 0) atomicOr(&st->capacity, 1u);
+}
+
 }  // namespace f64s
 
+// This file makes two objects (Makefile): the per-frame kernel and, with NXG_F64S_BACKLOG_TU
+// (nxg_decode_f64_seq_backlog.hip), the backlog kernel, which is compiled without the machine
+// loop-invariant code motion pass: around decode_tile's loop that pass keeps the 64-bit constants
+// of the wave-uniform comparisons in vector registers throughout (79 VGPRs, 6 waves per SIMD;
+// without it 63 and 8, like the per-frame kernel, whose code stays as it was).
+#ifndef NXG_F64S_BACKLOG_TU
 // One wave per WREC records; the grid covers the most records W bytes can hold (W / 12), and the
 // waves past the frame's last record exit after the head read. Everything before the loads is
 // wave-uniform (scalar registers): the head, the closed-form position of the wave's first record
@@ -422,49 +485,17 @@ __global__ __launch_bounds__(f64s::TPB) void nxg_f64s_kernel(const uint8_t* __re
     const uint64_t k0 = (blk * (TPB / 64) + w) * WREC;
     const uint64_t p0 = pos_of(i0, k0);
     if (p0 >= W || failed) return;
-    const uint64_t id0 = i0 + k0;
-    const uint32_t b = vl64(id0);
-    const uint64_t nxt = 1ull << (7 * b);  // the next width change (ids < 2^35: b <= 5)
-    const uint32_t L = 11u + b;
-    const uint32_t ks = nxt - id0 < WREC ? (uint32_t)(nxt - id0) : WREC;
-    const uint64_t pend = p0 + (uint64_t)ks * L + (uint64_t)(WREC - ks) * (L + 1);  // pos(k0 + WREC)
-    bool over = false, bad = b > 5;
-    if (!bad && pend + 48 <= W) {
-        // (ks == WREC: one id width in the whole wave -- all but at most four waves of a frame)
-        if (NXG_F64S_PAIR && NXG_F64S_UNIFORM && ks == WREC)
-            bad = emit_full_pairs_uniform<R>(wire, p0, L, k0, i0, oid, oval, cap, lane, over);
-        else
-            bad = NXG_F64S_PAIR
-                      ? emit_full_pairs<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over)
-                      : emit_full<R>(wire, W, p0, L, ks, k0, i0, oid, oval, cap, lane, over);
-    } else if (!bad) {
-        // near the frame's end: n = #{k < WREC : pos(k0 + k) < W} (pos increases by 12..16 per
-        // record); the frame's last record must end exactly at W
-        uint32_t n = WREC;
-        if (pend > W) {
-            uint32_t lo = 0, hi = WREC;  // pos(k0 + lo) < W <= pos(k0 + hi)
-            while (hi - lo > 1) {
-                const uint32_t mid = (lo + hi) / 2;
-                if (pos_of(i0, k0 + mid) < W) lo = mid;
-                else hi = mid;
-            }
-            n = hi;
-        }
-        const uint64_t pn = pos_of(i0, k0 + n);
-        if (pn == W && lane == 0) {  // this wave holds the frame's last record
-            st->n_rows = k0 + n;
-            st->path = 1;
-            st->diag[1] = 1;  // decoded by the sequential-id kernel (diagnostics)
-        }
-        if (pn < W && n < WREC) bad = true;  // (cannot happen: pos(k0 + n) >= W by the search)
-        else if (pn > W) bad = true;         // the frame does not end at a record boundary
-        else bad = emit_edge(wire, W, p0, L, ks, n, k0, i0, oid, oval, cap, lane, over);
-    }
-    if (__any(bad) && lane == 0) {
-        atomicOr(&st->irregular, 4u);  // ids do not count up by one: the length-run decoder
-        atomicOr(&st->fast_fail, 1u);
-    }
-    if (__any(over) && lane == 0) atomicOr(&st->capacity, 1u);
+    decode_tile<R>(wire, W, oid, oval, cap, st, i0, k0, p0, lane);
+}
+
+bool nxg_f64s_backlog_takes(uint64_t W) { return W > 0 && W < f64s::kXcdMin; }
+
+// K for a frame of W bytes on a grid of `waves` waves: the tiles of the most records W bytes can
+// hold (the per-frame kernel's grid), divided among the waves
+uint32_t nxg_f64s_tiles_per_wave(uint64_t W, uint32_t waves) {
+    const uint64_t wrec = 64ull * NXG_F64S_R_SMALL;
+    const uint64_t tiles = (W / 12 + 1 + wrec - 1) / wrec;
+    return (uint32_t)((tiles + waves - 1) / waves);
 }
 
 uint64_t nxg_dec_f64s_groups(uint64_t W) {
@@ -490,3 +521,112 @@ hipError_t nxg_launch_dec_f64s(const uint8_t* wire, uint64_t W, uint64_t* oid, u
                            NXG_F64S_LDS, s, wire, W, oid, oval, cap, flags, st, zst);
     return hipGetLastError();
 }
+#else
+// A backlog of up to kF64sBacklogMax frames in one launch of a resident grid. Wave gw (of `waves`
+// in the grid) walks the frames in backlog order and decodes up to K = tiles_per_wave tiles of
+// each, K = ceil(tiles(W) / waves) from the host: tiles gw, gw + waves, gw + 2 waves, ... (the
+// grid moves through a frame side by side, like the waves of the kernel above, and every wave
+// has work until the frame's last round; NXG_F64S_BL_STRIDE=0: tiles gw K .. gw K + K - 1, which
+// leaves the waves behind the frame's real end idle, one in five at 14.8 bytes a record, and was
+// slower than one launch per frame on one of two machines). Tile t is rows [t WREC, (t + 1) WREC)
+// as in the kernel above, so which wave writes which rows depends on the grid alone. No wave
+// ever waits for another. Two frames of one launch that write the same columns (the host allows
+// it for equal W only, and cuts the launch otherwise) have every row written by the same wave, in
+// backlog order; before the later frame (kF64sReuse) the wave waits for its own stores, so the
+// later frame's rows are the ones left.
+template <int R>
+__global__ __launch_bounds__(f64s::TPB) void nxg_f64s_backlog_kernel(const NxgF64sBacklog b) {
+    using namespace f64s;
+    using namespace f64rec16;
+    constexpr uint32_t WREC = 64 * R;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t gw = blockIdx.x * (TPB / 64) + w;
+#pragma unroll 1
+    for (uint32_t j = 0; j < b.n; j++) {
+        const NxgF64sFrame& f = b.f[j];
+        const uint8_t* __restrict__ wire = f.wire;
+        const uint64_t W = f.W;
+        DevStatus* __restrict__ st = f.st;
+        const uint32_t failed = st->fast_fail;
+        if (f.zst && gw == 0 && lane == 0) *f.zst = DevStatus{};
+        uint4 h0;
+        if (W >= 16) {
+            h0 = *reinterpret_cast<const uint4*>(wire);
+        } else {
+            uint32_t v[4] = {0, 0, 0, 0};
+            for (uint32_t k = 0; k < (uint32_t)W; k++) v[k >> 2] |= (uint32_t)wire[k] << (8 * (k & 3));
+            h0 = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        h0.x = (uint32_t)__builtin_amdgcn_readfirstlane((int)h0.x);
+        h0.y = (uint32_t)__builtin_amdgcn_readfirstlane((int)h0.y);
+        h0.z = (uint32_t)__builtin_amdgcn_readfirstlane((int)h0.z);
+        h0.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)h0.w);
+        const uint32_t hl = rec_check16(h0.x, h0.y, W);
+        if (!hl) {
+            if (gw == 0 && lane == 0) {
+                atomicOr(&st->irregular, 2u);  // not an f64 frame: the host goes on to the mixed path
+                atomicOr(&st->fast_fail, 1u);
+            }
+            continue;
+        }
+        if (failed) continue;
+        uint64_t i0, v0;
+        rec_decode16(h0.x, h0.y, h0.z, h0.w, hl, i0, v0);
+        // An earlier frame of this launch wrote these columns: this wave's stores to them first.
+        // The workgroup-scope release fence keeps the compiler from moving stores across, but on
+        // gfx950 it emits no instruction (a workgroup shares its compute unit's cache, so nothing
+        // is waited for); the wait on the wave's own vector-memory counter, vmcnt(0), is explicit.
+        if (f.flags & kF64sReuse) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0); expcnt and lgkmcnt not waited for
+        }
+        // (32 bits: a frame here has fewer than 2^17 tiles, and K waves < tiles + waves)
+        const uint32_t K = f.tiles_per_wave;
+#if NXG_F64S_BL_STRIDE
+        // tiles gw, gw + waves, ...: the waves of the grid move through the frame side by side
+        const uint32_t waves = gridDim.x * (TPB / 64);
+#pragma unroll 1
+        for (uint32_t t = 0, tile = gw; t < K; t++, tile += waves) {
+            const uint64_t k0 = (uint64_t)tile * WREC;
+            const uint64_t p0 = pos_of(i0, k0);
+            if (p0 >= W) break;
+            decode_tile<R>(wire, W, f.oid, f.oval, f.cap, st, i0, k0, p0, lane);
+        }
+        continue;
+#endif
+        uint64_t k0 = (uint64_t)(gw * K) * WREC;
+        uint64_t p0 = pos_of(i0, k0);
+#pragma unroll 1
+        for (uint32_t t = 0; t < K && p0 < W; t++) {
+            decode_tile<R>(wire, W, f.oid, f.oval, f.cap, st, i0, k0, p0, lane);
+            // pos(k0 + WREC), as decode_tile's pend (at most one width change in WREC records)
+            const uint32_t bw = vl64(i0 + k0);
+            if (bw > 5) break;  // (rejected there)
+            const uint64_t left = (1ull << (7 * bw)) - (i0 + k0);
+            p0 += (uint64_t)WREC * (11u + bw) + (left < WREC ? WREC - (uint32_t)left : 0u);
+            k0 += WREC;
+        }
+    }
+}
+
+// the workgroups the backlog kernel keeps resident on `ncu` compute units (for speed only)
+int nxg_f64s_backlog_wgs(int ncu) {
+    int occ = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, nxg_f64s_backlog_kernel<NXG_F64S_R_SMALL>,
+                                                     f64s::TPB, NXG_F64S_LDS) != hipSuccess) {
+        (void)hipGetLastError();
+        occ = 0;
+    }
+    return std::max(1, ncu) * std::max(1, occ);
+}
+
+// Frames b.f[0 .. b.n) (each nxg_f64s_backlog_takes, tiles_per_wave for 4 * wgs waves) in one launch.
+hipError_t nxg_launch_dec_f64s_backlog(const NxgF64sBacklog& b, int wgs, hipStream_t s) {
+    if (b.n == 0) return hipSuccess;
+    if (b.n > kF64sBacklogMax || wgs < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nxg_f64s_backlog_kernel<NXG_F64S_R_SMALL>, dim3((uint32_t)wgs),
+                       dim3(f64s::TPB), NXG_F64S_LDS, s, b);
+    return hipGetLastError();
+}
+#endif  // NXG_F64S_BACKLOG_TU

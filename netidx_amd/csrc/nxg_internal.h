@@ -119,6 +119,32 @@ hipError_t nxg_launch_dec_f64x(const uint8_t* wire, uint64_t W, uint64_t* oid, u
 uint64_t nxg_dec_f64s_groups(uint64_t W);
 hipError_t nxg_launch_dec_f64s(const uint8_t* wire, uint64_t W, uint64_t* oid, uint64_t* oval,
                                uint64_t cap, DevStatus* st, DevStatus* zst, hipStream_t s);
+// A backlog of such frames in one launch of a resident grid (nxg_f64s_backlog_kernel): frames
+// shorter than the Infinity Cache only (nxg_f64s_backlog_takes), at most kF64sBacklogMax, each with
+// its own status slot and zero slot. kF64sReuse marks a frame that writes the columns of an earlier
+// frame of the launch; that is allowed only where both have the same oid, oval, cap and W.
+constexpr uint32_t kF64sBacklogMax = 32;
+constexpr uint32_t kF64sReuse = 1;
+struct NxgF64sFrame {
+    const uint8_t* wire;
+    uint64_t W;
+    uint64_t* oid;
+    uint64_t* oval;
+    uint64_t cap;
+    DevStatus* st;
+    DevStatus* zst;
+    uint32_t tiles_per_wave;  // nxg_f64s_tiles_per_wave(W, 4 * the launch's workgroups)
+    uint32_t flags;
+};
+struct NxgF64sBacklog {
+    uint32_t n, pad;
+    NxgF64sFrame f[kF64sBacklogMax];
+};
+static_assert(sizeof(NxgF64sBacklog) <= 2560, "kernel arguments of the backlog kernel");
+bool nxg_f64s_backlog_takes(uint64_t W);
+uint32_t nxg_f64s_tiles_per_wave(uint64_t W, uint32_t waves);
+int nxg_f64s_backlog_wgs(int ncu);
+hipError_t nxg_launch_dec_f64s_backlog(const NxgF64sBacklog& b, int wgs, hipStream_t s);
 // f64 decode by length runs (nxg_decode_f64_run.hip): probe + emit launches. `desc` holds 16 bytes
 // per tile (nxg_dec_f64r_tiles(W)), `tstat` nxg_dec_f64r_groups(W) epoch-tagged words. Sets
 // DevStatus.irregular (and fast_fail) for frames whose record lengths vary record to record.

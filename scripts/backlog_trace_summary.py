@@ -7,7 +7,8 @@
                   (counters in a run of their own)
 and prints: the timed backlog's kernel mean, first launch call -> first kernel start, and every
 host call and other kernel after the last launch, relative to the end of the last
-nxg_f64s_kernel; the counters' means per launch.
+sequential-id decode kernel (nxg_f64s_kernel, one per frame, or nxg_f64s_backlog_kernel, one per
+group of frames: profiles/seq_group/); the counters' means per launch.
 usage: python3 scripts/backlog_trace_summary.py DIR > DIR/summary.json"""
 import collections
 import csv
@@ -33,23 +34,24 @@ if kt and ht:
                    "tid": r["Thread_Id"]} for r in csv.DictReader(open(ht))), key=lambda r: r["s"])
     main_tid = collections.Counter(a["tid"] for a in api if "LaunchKernel" in a["f"]).most_common(1)[0][0]
     api = [a for a in api if a["tid"] == main_tid]
-    # segments of launches between stream synchronizes: the timed backlog is the one with 20
-    # sequential-id kernels
-    f64 = [k for k in ks if "nxg_f64s_kernel" in k["name"]]
+    # segments of launches between stream synchronizes: the timed backlog is the one whose
+    # sequential-id kernels (per-frame or backlog) run longest
+    f64 = [k for k in ks if "nxg_f64s_" in k["name"]]
     res["kernel"] = {"name": f64[0]["name"].split("(")[0] if f64 else None, "launches": len(f64),
                      "mean_us_all": round(sum(k["e"] - k["s"] for k in f64) / max(1, len(f64)) / 1e3, 3)}
-    # the longest run of f64s kernels with no host sync in between
     syncs = [a for a in api if a["f"] == "hipStreamSynchronize" or a["f"] == "hipDeviceSynchronize"]
     bounds = [0] + [a["e"] for a in syncs] + [1 << 62]
     best = None
     for lo, hi in zip(bounds, bounds[1:]):
         la = [a for a in api if "LaunchKernel" in a["f"] and lo <= a["s"] < hi]
-        if best is None or len(la) > len(best[0]):
-            best = (la, lo, hi)
-    la, lo, hi = best
+        if not la:
+            continue
+        sk = [k for k in f64 if la[0]["s"] <= k["s"] < hi]
+        busy = sum(k["e"] - k["s"] for k in sk)
+        if sk and (best is None or busy > best[0]):
+            best = (busy, la, sk)
+    _, la, seg_k = best
     t_first_call = la[0]["s"]
-    seg_k = [k for k in f64 if k["s"] >= t_first_call]
-    seg_k = seg_k[:20]
     first_k, last_k = seg_k[0], seg_k[-1]
     burst = [k for k in ks if first_k["s"] <= k["s"] and k["s"] <= last_k["e"] + 2_000_000]
     last_any = max(k["e"] for k in burst if k["s"] <= last_k["e"] + 200_000)
@@ -57,6 +59,7 @@ if kt and ht:
     res["backlog"] = {
         "launch_calls_in_segment": len(la),
         "f64s_kernels": len(seg_k),
+        "f64s_kernel_names": sorted({k["name"].split("(")[0] for k in seg_k}),
         "kernel_mean_us": round(sum(k["e"] - k["s"] for k in seg_k) / len(seg_k) / 1e3, 3),
         "first_launch_call_to_first_kernel_start_us": round((first_k["s"] - t_first_call) / 1e3, 2),
         "first_launch_call_to_last_launch_return_us": round((la[-1]["e"] - t_first_call) / 1e3, 2),
