@@ -396,7 +396,12 @@ typedef struct NxgSubTable {
     const uint8_t* slot_has_last;     /* [n_slots]: 1 if the subscription keeps `last` */
     uint32_t n_chans;                 /* channels (ChanId) */
 } NxgSubTable;
-/* Output (device memory, capacities from the caller):
+/* A slot may name one channel more than once: each stream gets its own entry, in stream order
+ * (the reference dedups streams on subscribe, connection.rs:328-358; the table need not).
+ * n_chans == 0 is valid: chan_off[0] = 0 and no entries, last_row and n_unmatched as usual. So
+ * are a table with no slots and a batch in which no Id has one.
+ *
+ * Output (device memory, capacities from the caller):
  *   chan_off[n_chans + 1]  channel c's batch is entries [chan_off[c], chan_off[c+1])
  *   ent_sub[cap], ent_row[cap]  (SubId, index of the update's row in the decoded columns)
  *   last_row[n_slots]      1 + the last row of the slot's subscription in this batch, 0 if none

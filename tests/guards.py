@@ -7,6 +7,9 @@ write and check the sentinels afterwards:
   guarded_columns / assert_guards          decoder outputs: every array of a Columns holds
                                            `spare` elements behind its capacity
   guarded_buffer / assert_outside_untouched  encoder outputs: `margin` bytes on both sides
+  guarded_dispatch / assert_dispatch_guards  fan-out outputs (NxgDispatch): chan_off, ent_sub,
+                                           ent_row and last_row at exactly their capacities,
+                                           `spare` elements behind each
 
 The band is memory the test owns, so an overrun is seen, not faulted on.
 """
@@ -101,3 +104,54 @@ def assert_outside_untouched(buf, off, n):
                 f"{len(bad)} bytes {side} the output were written: offsets {base + int(bad[0])} .. "
                 f"{base + int(bad[-1])} relative to out (the output is [0, {n}), phase "
                 f"{lo % 16})")
+
+
+DISPATCH_ARRAYS = ("chan_off", "ent_sub", "ent_row", "last_row")
+
+
+class GuardedDispatch:
+    """Caller-owned outputs of nxg_dispatch_updates / nxg_publish_commit (uint64 arrays held as
+    int64 tensors): `caps[name]` elements the call may write, `spare` behind them, every byte
+    SENTINEL."""
+
+    def __init__(self, t, caps, spare):
+        self.t, self.guard_caps, self.guard_spare = t, caps, spare
+
+    def struct(self):
+        """The NxgDispatch that states the capacities."""
+        from netidx_amd.codec import NxgDispatch
+        return NxgDispatch(self.guard_caps["ent_sub"], *(self.t[k].data_ptr()
+                                                         for k in DISPATCH_ARRAYS), 0, 0)
+
+    def host(self, name, n=None):
+        """Host copy (uint64) of the first n (default: the capacity) elements of an array."""
+        n = self.guard_caps[name] if n is None else n
+        return self.t[name][:n].cpu().numpy().view(np.uint64)
+
+
+def guarded_dispatch(n_chans, n_slots, cap_entries, device="cuda", spare=MIN_SPARE):
+    """chan_off[n_chans + 1], ent_sub[cap_entries], ent_row[cap_entries], last_row[n_slots], each
+    followed by `spare` (at least 512) guard elements."""
+    import torch
+    spare = max(int(spare), MIN_SPARE)
+    caps = {"chan_off": int(n_chans) + 1, "ent_sub": int(cap_entries),
+            "ent_row": int(cap_entries), "last_row": int(n_slots)}
+    t = {k: torch.full(((c + spare) * 8,), SENTINEL, dtype=torch.uint8,
+                       device=device).view(torch.int64) for k, c in caps.items()}
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize(device)  # the codec runs on its own stream
+    return GuardedDispatch(t, caps, spare)
+
+
+def assert_dispatch_guards(g):
+    """Every element in [cap, cap + spare) of the four arrays still holds the sentinel."""
+    for name in DISPATCH_ARRAYS:
+        cap, spare = g.guard_caps[name], g.guard_spare
+        b, isz = _host_bytes(g.t[name])
+        assert len(b) == (cap + spare) * isz, (name, len(b), cap, spare, isz)
+        bad = np.flatnonzero(b[cap * isz:] != SENTINEL)
+        if len(bad):
+            raise AssertionError(
+                f"{name}[{cap + int(bad[0]) // isz}] was written: the capacity is {cap} "
+                f"({len(np.unique(bad // isz))} elements of the guard band changed, the last at "
+                f"{cap + int(bad[-1]) // isz})")

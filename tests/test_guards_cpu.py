@@ -1,5 +1,6 @@
 """The guard helpers (tests/guards.py) catch what they are for: a planted one-element overrun in
-each column array, a planted byte on either side of an encoder buffer; and pass on clean data."""
+each column array or fan-out output, a planted byte on either side of an encoder buffer; and pass
+on clean data."""
 import types
 
 import numpy as np
@@ -89,3 +90,48 @@ def test_buffer_guards(off):
     # a shorter claim (a failed encode with cap < n): the bytes from cap on are guarded too
     with pytest.raises(AssertionError, match=r"behind the output"):
         guards.assert_outside_untouched(buf, off, n - 1)
+
+
+DISPATCH_CAPS = {"chan_off": 5, "ent_sub": 9, "ent_row": 9, "last_row": 0}
+
+
+def fake_dispatch(caps, spare):
+    """What guarded_dispatch returns, on numpy arrays."""
+    t = {k: np.full((c + spare) * 8, guards.SENTINEL, np.uint8).view(np.int64)
+         for k, c in caps.items()}
+    return guards.GuardedDispatch(t, dict(caps), spare)
+
+
+def test_dispatch_guards_name_a_planted_overrun():
+    g = fake_dispatch(DISPATCH_CAPS, 512)
+    for name in guards.DISPATCH_ARRAYS:  # below the capacity anything may be written
+        g.t[name][: DISPATCH_CAPS[name]] = 0
+    guards.assert_dispatch_guards(g)
+    for name in guards.DISPATCH_ARRAYS:
+        for at in (DISPATCH_CAPS[name], DISPATCH_CAPS[name] + 511):
+            keep = int(g.t[name][at])
+            g.t[name][at] = 7
+            with pytest.raises(AssertionError, match=rf"^{name}\[{at}\] was written: the "
+                                                     rf"capacity is {DISPATCH_CAPS[name]} "):
+                guards.assert_dispatch_guards(g)
+            g.t[name][at] = keep
+            guards.assert_dispatch_guards(g)
+    # one changed byte of an element is seen
+    g.t["ent_row"].view(np.uint8)[(DISPATCH_CAPS["ent_row"] + 3) * 8 + 6] ^= 1
+    with pytest.raises(AssertionError, match=r"^ent_row\[12\] was written"):
+        guards.assert_dispatch_guards(g)
+
+
+def test_guarded_dispatch_capacities_on_the_host():
+    g = guards.guarded_dispatch(4, 0, 9, device="cpu")
+    assert g.guard_caps == DISPATCH_CAPS and g.guard_spare >= 512
+    assert {k: v.numel() for k, v in g.t.items()} == {k: c + g.guard_spare
+                                                      for k, c in DISPATCH_CAPS.items()}
+    guards.assert_dispatch_guards(g)
+    s = g.struct()
+    assert s.cap_entries == 9 and s.chan_off == g.t["chan_off"].data_ptr()
+    assert s.ent_sub == g.t["ent_sub"].data_ptr() and s.ent_row == g.t["ent_row"].data_ptr()
+    assert s.last_row == g.t["last_row"].data_ptr()
+    g.t["last_row"][0] = 1  # capacity 0: the first element is already the band
+    with pytest.raises(AssertionError, match=r"^last_row\[0\] was written"):
+        guards.assert_dispatch_guards(g)
