@@ -454,7 +454,8 @@ bool nxg_dispatch_updates(NxgCtx* ctx, const NxgSubTable* tab, const uint64_t* i
  * rows the call processes, the j-th NO_WID row in row order gets fresh_wid + j, and n_fresh says
  * how many were used. Replies and the wait list carry the effective id; the columns are not
  * modified.
- * Subscribe needs a path lookup and stays with the host: the call stops in front of the first
+ * Subscribe needs a path lookup and is not this call's (the host's, or nxg_route_subscribes',
+ * below, which alternates with this call through a mixed frame): the call stops in front of the first
  * Subscribe span at or after ctl_begin and says where (below). Also left to the host: creating
  * the SendResult of each wait-list entry, gc_on_write, its own unsubscribe() bookkeeping from
  * unsub_id[], and building the WriteRequests (path, client, value) from the entries.
@@ -521,6 +522,144 @@ typedef struct NxgWriteRoute {
 bool nxg_route_writes(NxgCtx* ctx, const NxgWriteTable* tab, const uint8_t* frame,
                       const NxgColumns* cols, const NxgWriteCols* wcols, uint64_t row_begin,
                       uint64_t ctl_begin, uint64_t fresh_wid, NxgWriteRoute* out, NetidxError* err);
+
+/* ---- a device-resident by_path: path (its exact bytes) -> publisher::Id ----------------------
+ * PublisherInner.by_path (netidx/src/publisher/mod.rs) as a hash table in device memory, built
+ * and queried on the device: open addressing with a stored 64-bit hash, a hit confirmed by
+ * comparing every byte of the path (a hash match alone is never an answer). The table owns a copy
+ * of the inserted bytes. It holds at most cap_paths paths in slots sized so that they stay at or
+ * below half full, and cap_bytes bytes of paths; the bytes of a removed path are not reclaimed
+ * (cap_bytes bounds what was ever inserted). Keys are canonical paths: the host canonises what it
+ * inserts (nxg_path_is_plain says when the bytes already are). One thread at a time per table; a
+ * table belongs to the device of the ctx that made it. */
+typedef struct NxgPathTable NxgPathTable;
+#define NXG_NO_ID UINT64_MAX
+NxgPathTable* nxg_path_table_new(NxgCtx* ctx, uint64_t cap_paths, uint64_t cap_bytes,
+                                 NetidxError* err);
+void nxg_path_table_free(NxgPathTable* t);
+uint64_t nxg_path_table_len(const NxgPathTable* t);
+/* Host arrays: path i is paths[off[i] .. off[i+1]) and maps to id[i] (never NXG_NO_ID). The
+ * result does not depend on scheduling: a path already in the table keeps its Id; among equal
+ * paths of one call the lowest index wins; *n_dup (may be NULL) counts the losers of both kinds.
+ * len + n > cap_paths, or more bytes than the table has left, is refused (NXG_CAPACITY in the
+ * message) before anything changes. Synchronous. */
+bool nxg_path_table_insert(NxgCtx* ctx, NxgPathTable* t, const uint8_t* paths, const uint64_t* off,
+                           const uint64_t* id, uint64_t n, uint64_t* n_dup, NetidxError* err);
+/* Removing leaves a tombstone that lookups probe past and later inserts reuse; a path that is
+ * absent (or named a second time in the call) counts in *n_missing (may be NULL). Synchronous. */
+bool nxg_path_table_remove(NxgCtx* ctx, NxgPathTable* t, const uint8_t* paths, const uint64_t* off,
+                           uint64_t n, uint64_t* n_missing, NetidxError* err);
+/* Device arrays: path i is dheap[doff[i] .. doff[i] + dlen[i]); did_out[i] = its Id, or NXG_NO_ID.
+ * The paths are read in aligned 8-byte words: dheap must be readable up to the next multiple of 8
+ * past its last path (any allocation is). What Publisher::id(path) answers. Synchronous. */
+bool nxg_path_table_lookup(NxgCtx* ctx, const NxgPathTable* t, const uint8_t* dheap,
+                           const uint64_t* doff, const uint32_t* dlen, uint64_t n,
+                           uint64_t* did_out, NetidxError* err);
+/* A path is plain if it has no `\` byte, is not empty, has no `//` and no trailing `/` (unless it
+ * is exactly `/`). Path::decode canonises (netidx-core/src/path.rs:24-48, 70-72, 131-139) and its
+ * splitting honours `\` escapes; a plain path is canonical as it stands, so its wire bytes are
+ * the by_path key. Host-side, no ctx. */
+bool nxg_path_is_plain(const uint8_t* path, uint64_t len);
+
+/* ---- Subscribe routing: replaces the Subscribe arm of ClientCtx::handle_batch_inner
+ * (netidx/src/publisher/server.rs:506-549) and subscribe() (server.rs:60-137) -----------------
+ * One run of consecutive Subscribe spans of a decoded To frame (nxg_decode_writes, device
+ * columns; the decode validated each path's UTF-8). The run is spans k = ctl_begin, ctl_begin + 1,
+ * ... for as long as ctl_variant[k] == 0, ctl_row[k] == row_begin (no Write row lies in between)
+ * and the path is plain (nxg_path_is_plain). On return next_ctl is the span the run ended in
+ * front of, and `stopped` says why:
+ *   0  the end of the spans
+ *   1  span next_ctl is an Unsubscribe, or a Write row comes first: the host continues with
+ *      nxg_route_writes(row_begin, next_ctl), which is unchanged and still stops in front of the
+ *      next Subscribe (then: next_row / next_ctl - 1 of that call go in here)
+ *   2  span next_ctl is a Subscribe whose path is not plain: the host handles that one message
+ *      and resumes at next_ctl + 1
+ * The two calls alternate through a mixed frame; between them the host updates perm_of_id from
+ * sub_id[] / sub_perm[] (and unsub_id[]). A frame of Subscribes only takes one call.
+ * Per span, in the reference's order (server.rs:68-135):
+ *   NXG_SUB_DENIED         span_perm[k] == NXG_SUB_PERM_DENY (server.rs:520-535), or the path
+ *       resolves, by_id has the Id and allow_of_id[id] == 0 (server.rs:98-106): Denied(path)
+ *   NXG_SUB_DEFERRED       the path is not in by_path, the greatest default base <= path (byte
+ *       order) is a byte prefix of it, and fewer than deferred_room spans of this call were
+ *       deferred before it: no reply, the span's index goes to deferred[]. Only that one base is
+ *       examined, as the loop of server.rs:74-93 does: with bases /a and /a/b the path /a/c gets
+ *       NoSuchValue although /a is a prefix; with base /d the path /dx is deferred (starts_with
+ *       is a string prefix). The `continue` on a closed channel (server.rs:81) is the host's: it
+ *       lists the bases of open channels only.
+ *   NXG_SUB_NO_SUCH_VALUE  the path is not in by_path, otherwise: NoSuchValue(path)
+ *   NXG_SUB_IGNORED        the path resolves, but id >= n_ids or slot_of_id[id] == NXG_NO_SLOT
+ *       (by_id.get_mut is None, server.rs:97): nothing
+ *   NXG_SUB_SUBSCRIBED     otherwise: Subscribed(path, id, current), and (id, permissions) is
+ *       appended to sub_id[] / sub_perm[] (cl.subscribed.insert, server.rs:109). The same path
+ *       twice gives two replies and two entries, as the reference does.
+ * The reply frame holds the replies in span order, L = lw(|body|):
+ *   NoSuchValue(path)            varint(L) 00 varint(|p|) p
+ *   Denied(path)                 varint(L) 01 varint(|p|) p
+ *   Subscribed(path, id, value)  varint(L) 03 varint(|p|) p varint(id) Value
+ * with the current value of every tag encoded as nxg_encode_updates encodes it (text, Decimal,
+ * Abstract, nested Array / Map / Error(Value) from the table's children).
+ * Left to the host: the hc_subscribed interning and the ut.subscribed update from sub_id[]
+ * (server.rs:111-124), wait_clients (127-131), Event::Subscribe (132), sending the deferred paths
+ * to their default channels (80-85), the gc of hc_subscribed (569-571), check_token (its SHA3)
+ * and extended_auth, whose results come in as span_perm[] and allow_of_id[]. */
+#define NXG_SUB_PERM_DENY 0xffffffffu
+enum NxgSubscribeOutcome {
+    NXG_SUB_SUBSCRIBED = 0,
+    NXG_SUB_NO_SUCH_VALUE = 1,
+    NXG_SUB_DENIED = 2,
+    NXG_SUB_DEFERRED = 3,
+    NXG_SUB_IGNORED = 4
+};
+/* Built by the host; every array is device memory (the two structs themselves are host memory) */
+typedef struct NxgSubscribeTable {
+    const NxgPathTable* paths;     /* by_path */
+    const struct NxgPubTable* pub; /* by_id: n_ids, slot_of_id, n_slots and the cur_* columns of
+                                      the current values (the client CSR is not read) */
+    const uint8_t* allow_of_id;    /* [n_ids]: extended_auth evaluated for this client, 0 denies;
+                                      NULL: no extended_auth */
+    uint64_t n_defaults;           /* the default publishers' bases (open channels only), sorted */
+    const uint8_t* default_heap;   /* ascending in byte order and unique: base b is */
+    const uint64_t* default_off;   /* default_heap[default_off[b] .. default_off[b+1]) */
+    uint64_t deferred_room;        /* MAX_DEFERRED - deferred_subs.inner().len(), server.rs:56, 78 */
+} NxgSubscribeTable;
+/* Capacities and device arrays from the caller, counts written by the call. A-priori bounds for
+ * K spans: sub <= K, deferred <= min(K, deferred_room), reply bytes <= the spans' bytes + K * (15
+ * + the longest current value). */
+typedef struct NxgSubscribeRoute {
+    uint64_t cap_spans;    /* outcome[] / span_id[] entries, >= cols->n_ctl */
+    uint8_t* outcome;      /* [cap_spans]: NxgSubscribeOutcome of span k, for the run's spans */
+    uint64_t* span_id;     /* [cap_spans]: the Id the span's path resolves to, or NXG_NO_ID */
+    uint64_t cap_sub;      /* the Subscribed spans' (Id, Permissions bits), in order */
+    uint64_t* sub_id;
+    uint32_t* sub_perm;
+    uint64_t cap_deferred; /* the deferred spans' indices, in order */
+    uint64_t* deferred;
+    uint64_t cap_reply;    /* the reply frame's payload */
+    uint8_t* reply;
+    /* written by the call */
+    uint64_t n_spans;      /* spans of the run: next_ctl - ctl_begin */
+    uint64_t n_sub, n_deferred;
+    uint64_t n_replies;    /* messages in `reply` */
+    uint64_t reply_len;    /* bytes in `reply` */
+    uint64_t n_outcome[5]; /* the run's spans per NxgSubscribeOutcome */
+    uint64_t next_ctl;
+    uint32_t stopped;      /* 0, 1 or 2, above */
+    uint32_t pad;
+} NxgSubscribeRoute;
+/* `frame` is the device frame the columns were decoded from (the paths are read from it, in
+ * aligned 8-byte words). span_perm (device memory) is indexed by the absolute span index: NULL is
+ * DesiredAuth::Anonymous, every Subscribe gets Permissions::all() = 0x3f (resolver_server/
+ * auth.rs:24-29); otherwise the host has looked up the resolver's secret and run check_token
+ * (server.rs:244-271) and passes the permission bits, or NXG_SUB_PERM_DENY for "no stored secret"
+ * and "token invalid" alike. One synchronisation; synchronous. Returns false on misuse (the
+ * message names the field: host or F64-layout columns, a missing array, ctl_begin > n_ctl, a
+ * pointer that is not device memory), on a HIP failure, when a current value cannot be encoded
+ * (an unknown tag, nesting past NXG_MAX_DEPTH), or when a capacity is exceeded (NXG_CAPACITY in
+ * the message); the counts then hold the required values (n_sub, n_deferred, reply_len) and the
+ * arrays hold what fitted, as nxg_route_writes does. */
+bool nxg_route_subscribes(NxgCtx* ctx, const NxgSubscribeTable* tab, const uint8_t* frame,
+                          const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
+                          const uint32_t* span_perm, NxgSubscribeRoute* out, NetidxError* err);
 
 /* ---- type-partitioned view of decoded mixed columns (optional output) --------
  * Replaces the per-value 28-way `match` on the tag (Value::decode, netidx-value/src/lib.rs:470-506)

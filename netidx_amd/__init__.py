@@ -16,7 +16,9 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES, ArchiveImage,
                     WindowCapacity, WriteTable, WriteRoute, RouteCapacity, NOT_SUBSCRIBED,
                     PERM_WRITE, WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED,
-                    WRITE_NOT_ACCEPTED)
+                    WRITE_NOT_ACCEPTED, PathTable, SubscribeTable, SubscribeRoute, path_is_plain,
+                    NO_ID, SUB_PERM_DENY, PERM_ALL, SUB_SUBSCRIBED, SUB_NO_SUCH_VALUE, SUB_DENIED,
+                    SUB_DEFERRED, SUB_IGNORED, MAX_DEFERRED)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
            "frame_split", "frame_header", "frame_parse_header", "LAYOUT_F64", "LAYOUT_MIXED",
@@ -28,4 +30,7 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "ResolverClient", "TagView", "TAG_BINS", "WriteCols", "NxgWriteCols", "WRITE_REPLY",
            "WRITE_NO_WID", "PATH_WRITES", "ArchiveImage", "WindowCapacity", "WriteTable",
            "WriteRoute", "RouteCapacity", "NOT_SUBSCRIBED", "PERM_WRITE", "WRITE_ROUTED",
-           "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED"]
+           "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED", "PathTable",
+           "SubscribeTable", "SubscribeRoute", "path_is_plain", "NO_ID", "SUB_PERM_DENY",
+           "PERM_ALL", "SUB_SUBSCRIBED", "SUB_NO_SUCH_VALUE", "SUB_DENIED", "SUB_DEFERRED",
+           "SUB_IGNORED", "MAX_DEFERRED"]

@@ -120,6 +120,23 @@ class NxgWriteRoute(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+class NxgSubscribeTable(C.Structure):
+    _fields_ = [("paths", C.c_void_p), ("pub", C.c_void_p), ("allow_of_id", C.c_void_p),
+                ("n_defaults", C.c_uint64), ("default_heap", C.c_void_p),
+                ("default_off", C.c_void_p), ("deferred_room", C.c_uint64)]
+
+
+class NxgSubscribeRoute(C.Structure):
+    _fields_ = [("cap_spans", C.c_uint64), ("outcome", C.c_void_p), ("span_id", C.c_void_p),
+                ("cap_sub", C.c_uint64), ("sub_id", C.c_void_p), ("sub_perm", C.c_void_p),
+                ("cap_deferred", C.c_uint64), ("deferred", C.c_void_p),
+                ("cap_reply", C.c_uint64), ("reply", C.c_void_p),
+                ("n_spans", C.c_uint64), ("n_sub", C.c_uint64), ("n_deferred", C.c_uint64),
+                ("n_replies", C.c_uint64), ("reply_len", C.c_uint64),
+                ("n_outcome", C.c_uint64 * 5), ("next_ctl", C.c_uint64),
+                ("stopped", C.c_uint32), ("pad", C.c_uint32)]
+
+
 TAG_BINS = 256
 
 
@@ -239,6 +256,24 @@ SIGNATURES = {
                                     C.POINTER(NxgColumns), C.POINTER(NxgWriteCols), C.c_uint64,
                                     C.c_uint64, C.c_uint64, C.POINTER(NxgWriteRoute),
                                     C.POINTER(NetidxError)]),
+    "nxg_path_table_new": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_uint64,
+                                        C.POINTER(NetidxError)]),
+    "nxg_path_table_free": (None, [C.c_void_p]),
+    "nxg_path_table_len": (C.c_uint64, [C.c_void_p]),
+    "nxg_path_table_insert": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                         C.POINTER(NetidxError)]),
+    "nxg_path_table_remove": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_uint64, C.POINTER(C.c_uint64),
+                                         C.POINTER(NetidxError)]),
+    "nxg_path_table_lookup": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.POINTER(NetidxError)]),
+    "nxg_path_is_plain": (C.c_bool, [C.c_void_p, C.c_uint64]),
+    "nxg_route_subscribes": (C.c_bool, [C.c_void_p, C.POINTER(NxgSubscribeTable), C.c_void_p,
+                                        C.POINTER(NxgColumns), C.c_uint64, C.c_uint64,
+                                        C.c_void_p, C.POINTER(NxgSubscribeRoute),
+                                        C.POINTER(NetidxError)]),
     "nxg_decode_range": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                     C.POINTER(NxgColumns), C.POINTER(NxgRange),
                                     C.POINTER(NetidxError)]),
@@ -1008,6 +1043,60 @@ class Codec:
         r.row_begin = row_begin
         return r
 
+    def route_subscribes(self, table, frame, cols, row_begin=0, ctl_begin=0, span_perm=None,
+                         cap_sub=None, cap_deferred=None, cap_reply=None):
+        """handle_batch_inner's Subscribe arm and subscribe() (publisher/server.rs:60-137, 506-549)
+        for one run of consecutive Subscribe spans of a decoded To frame, from span ctl_begin on:
+        `frame` is the device tensor decode_writes read, `cols` what it returned, `table` a
+        SubscribeTable, `span_perm` None (Anonymous) or a sequence / device tensor of n_ctl
+        permission words (SUB_PERM_DENY: Denied). Returns a SubscribeRoute: outcome and Id per
+        span, the subscribed (Id, permissions), the deferred spans, the reply frame, next_ctl and
+        `stopped` (0 the end, 1 continue with route_writes, 2 a path the host must handle).
+        Capacities default to the a-priori bounds; one that is exceeded raises RouteCapacity
+        carrying the required counts."""
+        import torch
+        dev = cols.device
+        n_ctl = int(cols.s.n_ctl)
+        spans = max(n_ctl - ctl_begin, 0)
+        cap_sub = spans if cap_sub is None else cap_sub
+        cap_deferred = min(spans, table.deferred_room) if cap_deferred is None else cap_deferred
+        if not hasattr(frame, "data_ptr") or frame.device.type != "cuda":
+            raise CodecError("frame: the device tensor the columns were decoded from")
+        if cap_reply is None:
+            cap_reply = frame.numel() + spans * (21 + table.max_value_len)
+
+        def buf(n, dt=torch.int64):
+            return torch.empty(max(int(n), 1), dtype=dt, device=dev)
+
+        r = SubscribeRoute()
+        r.ctl_begin = ctl_begin
+        r.outcome = buf(n_ctl, torch.uint8)
+        r.span_id = buf(n_ctl)
+        r.sub_id, r.sub_perm = buf(cap_sub), buf(cap_sub, torch.int32)
+        r.deferred = buf(cap_deferred)
+        r.reply = buf(cap_reply, torch.uint8)
+        if span_perm is not None and not hasattr(span_perm, "data_ptr"):
+            span_perm = torch.as_tensor(np.array(span_perm, dtype=np.uint32).view(np.int32)).to(dev)
+        r.span_perm = span_perm  # (kept alive through the call)
+        torch.cuda.synchronize(dev)
+        s = r.s
+        s.cap_spans, s.outcome, s.span_id = max(n_ctl, 1), r.outcome.data_ptr(), r.span_id.data_ptr()
+        s.cap_sub, s.sub_id, s.sub_perm = cap_sub, r.sub_id.data_ptr(), r.sub_perm.data_ptr()
+        s.cap_deferred, s.deferred = cap_deferred, r.deferred.data_ptr()
+        s.cap_reply, s.reply = cap_reply, r.reply.data_ptr()
+        tb = table.c_struct()
+        err = NetidxError()
+        ok = lib().nxg_route_subscribes(
+            self.ctx, C.byref(tb), C.c_void_p(frame.data_ptr()), C.byref(cols.s), row_begin,
+            ctl_begin, C.c_void_p(span_perm.data_ptr() if span_perm is not None else 0),
+            C.byref(s), C.byref(err))
+        if not ok and err.msg and b"NXG_CAPACITY" in err.msg:
+            msg = err.msg.decode()
+            lib().nxg_error_free(C.byref(err))
+            raise RouteCapacity(msg, r)
+        _check(ok, err)
+        return r
+
     def decode_range(self, dframe, frame_len, begin, end, cols):
         """Decode the messages that start in [begin, end) of a device frame (rows at cols[0:]);
         returns the NxgRange summary (entry / exit / n_rows / ok)."""
@@ -1273,12 +1362,264 @@ class WriteRoute:
 
 
 class RouteCapacity(CodecError):
-    """nxg_route_writes: a capacity was exceeded; `route` holds the required counts (n_entries,
-    n_wait, n_unsub, reply_len)."""
+    """nxg_route_writes / nxg_route_subscribes: a capacity was exceeded; `route` holds the required
+    counts (n_entries, n_wait, n_unsub, reply_len / n_sub, n_deferred, reply_len)."""
 
     def __init__(self, msg, route):
         super().__init__(msg)
         self.route = route
+
+
+NO_ID = (1 << 64) - 1
+SUB_PERM_DENY = 0xFFFFFFFF
+PERM_ALL = 0x3F  # Permissions::all() (resolver_server/auth.rs:24-29)
+SUB_SUBSCRIBED, SUB_NO_SUCH_VALUE, SUB_DENIED, SUB_DEFERRED, SUB_IGNORED = 0, 1, 2, 3, 4
+MAX_DEFERRED = 1000000  # publisher/server.rs:56
+
+
+def path_is_plain(path):
+    """nxg_path_is_plain: no `\\`, not empty, no `//`, no trailing `/` unless the path is `/`."""
+    p = path.encode() if isinstance(path, str) else bytes(path)
+    b = (C.c_uint8 * max(len(p), 1)).from_buffer_copy(p + b"\0")
+    return bool(lib().nxg_path_is_plain(b, len(p)))
+
+
+def _pack_paths(paths):
+    ps = [p.encode() if isinstance(p, str) else bytes(p) for p in paths]
+    off = np.zeros(len(ps) + 1, np.uint64)
+    off[1:] = np.cumsum([len(p) for p in ps], dtype=np.uint64)
+    heap = np.frombuffer(b"".join(ps) or b"\0", np.uint8).copy()
+    return ps, heap, off
+
+
+class PathTable:
+    """A device-resident by_path (nxg_path_table_*): path bytes -> publisher::Id, built and queried
+    on the GPU. At most cap_paths paths and cap_bytes bytes of paths."""
+
+    def __init__(self, codec, cap_paths, cap_bytes):
+        err = NetidxError()
+        self.codec = codec
+        self.h = lib().nxg_path_table_new(codec.ctx, cap_paths, cap_bytes, C.byref(err))
+        if not self.h:
+            _check(False, err)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().nxg_path_table_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    def __len__(self):
+        return int(lib().nxg_path_table_len(self.h))
+
+    def insert(self, paths, ids):
+        """paths[i] -> ids[i]; returns n_dup (paths already present, or equal to a path earlier
+        in the call: the earlier one wins)."""
+        ps, heap, off = _pack_paths(paths)
+        idv = np.array(ids, dtype=np.uint64)
+        assert len(idv) == len(ps)
+        dup, err = C.c_uint64(), NetidxError()
+        _check(lib().nxg_path_table_insert(self.codec.ctx, self.h, heap.ctypes.data,
+                                           off.ctypes.data, idv.ctypes.data, len(ps),
+                                           C.byref(dup), C.byref(err)), err)
+        return int(dup.value)
+
+    def remove(self, paths):
+        """Returns n_missing."""
+        ps, heap, off = _pack_paths(paths)
+        miss, err = C.c_uint64(), NetidxError()
+        _check(lib().nxg_path_table_remove(self.codec.ctx, self.h, heap.ctypes.data,
+                                           off.ctypes.data, len(ps), C.byref(miss),
+                                           C.byref(err)), err)
+        return int(miss.value)
+
+    def lookup_device(self, dheap, doff, dlen, n=None):
+        """Device tensors (uint8 bytes, int64 offsets, int32 lengths) -> an int64 device tensor of
+        Ids (NO_ID as -1)."""
+        import torch
+        n = doff.numel() if n is None else n
+        out = torch.empty(max(n, 1), dtype=torch.int64, device=doff.device)
+        err = NetidxError()
+        _check(lib().nxg_path_table_lookup(self.codec.ctx, self.h, _ptr(dheap), _ptr(doff),
+                                           _ptr(dlen), n, _ptr(out), C.byref(err)), err)
+        return out[:n]
+
+    def lookup(self, paths, device="cuda"):
+        """Host paths -> a list of Ids (NO_ID where the table has none)."""
+        import torch
+        ps, heap, off = _pack_paths(paths)
+        if not ps:
+            return []
+        dheap = torch.from_numpy(heap).to(device)
+        doff = torch.from_numpy(off[:-1].view(np.int64).copy()).to(device)
+        dlen = torch.from_numpy(np.diff(off).astype(np.uint32).view(np.int32)).to(device)
+        out = self.lookup_device(dheap, doff, dlen, len(ps))
+        return out.cpu().numpy().view(np.uint64).tolist()
+
+
+def _value_len(v):
+    """|Value::encode| of a (tag, payload) value (the model of tests/golden/make_golden.py)."""
+    def vl(x):
+        return (((x | 1).bit_length() - 1) * 9 + 73) >> 6
+    t, p = v
+    if t in (0, 2, 8):
+        return 5
+    if t in (1, 5):
+        return 1 + vl(p)
+    if t in (3, 7):
+        bits = 32 if t == 3 else 64
+        return 1 + vl(((p << 1) ^ (p >> (bits - 1))) & ((1 << bits) - 1))
+    if t in (4, 6, 9):
+        return 9
+    if t in (10, 11):
+        return 13
+    if t in (12, 13, 18):
+        return 1 + vl(len(p)) + len(p)
+    if t in (14, 15, 16):
+        return 1
+    if t == 19:
+        return 1 + vl(len(p)) + sum(_value_len(e) for e in p)
+    if t == 20:
+        return 17
+    if t == 21:
+        return 1 + vl(len(p)) + sum(_value_len(k) + _value_len(x) for k, x in p)
+    if t == 22:
+        return 1 + _value_len(p)
+    if t in (23, 24):
+        return 2
+    if t in (25, 26):
+        return 3
+    if t == 27:
+        n = len(p)
+        return 1 + n + vl(n + vl(n))
+    raise ValueError(t)
+
+
+def _flatten_value(v, kids, heap):
+    """The (tag, fixed, aux) slot of a (tag, payload) value: a container's elements go to `kids`
+    in one block, depth-first; text, Decimal and Abstract bytes are appended to `heap`."""
+    M = (1 << 64) - 1
+    t, p = v
+    if t in (2, 3, 6, 7, 24, 26):
+        return (t, p & M, 0)
+    if t in (0, 1, 4, 5, 8, 9, 23, 25):
+        return (t, p, 0)
+    if t in (10, 11):
+        return (t, p[0] & M, p[1])
+    if t in (12, 13, 18, 20, 27):
+        off = len(heap)
+        heap += p
+        return (t, off, len(p))
+    if t in (14, 15, 16):
+        return (t, 1 if t == 14 else 0, 0)
+    if t in (19, 21, 22):
+        elems = list(p) if t == 19 else ([x for kv in p for x in kv] if t == 21 else [p])
+        base = len(kids)
+        kids.extend([None] * len(elems))
+        for i, e in enumerate(elems):
+            kids[base + i] = _flatten_value(e, kids, heap)
+        return (t, base, 1 if t == 22 else len(p))
+    raise ValueError(t)
+
+
+class SubscribeTable:
+    """Device-resident publisher state for Subscribe routing (include/nxg_codec.h
+    NxgSubscribeTable): by_path (a PathTable), by_id and the current values (a PubTable),
+    extended_auth as allow_of_id, the default publishers' bases (sorted) and deferred_room."""
+
+    def __init__(self, paths, pub, allow_of_id=None, defaults=(), deferred_room=MAX_DEFERRED,
+                 max_value_len=9, device="cuda"):
+        import torch
+        self.paths, self.pub = paths, pub
+        self.allow_of_id = None if allow_of_id is None else torch.as_tensor(
+            np.array(allow_of_id, dtype=np.uint8, copy=True)).to(device)
+        bases = sorted(set(b.encode() if isinstance(b, str) else bytes(b) for b in defaults))
+        _, heap, off = _pack_paths(bases)
+        self.n_defaults = len(bases)
+        self.default_heap = torch.from_numpy(heap).to(device)
+        self.default_off = torch.from_numpy(off.view(np.int64).copy()).to(device)
+        self.deferred_room = int(deferred_room)
+        self.max_value_len = int(max_value_len)
+
+    @classmethod
+    def from_state(cls, codec, by_path, by_id, n_ids=None, denied_ids=None, defaults=(),
+                   deferred_room=MAX_DEFERRED, device="cuda"):
+        """by_path: {path bytes: id}; by_id: {id: value}, a value being (tag, payload) as in
+        tests/golden/make_golden.py (an Array's payload a list of values, a Map's a list of
+        pairs); denied_ids: the Ids extended_auth denies this client (None: no extended_auth);
+        defaults: the open default publishers' bases. n_ids: slot_of_id's extent (default: one
+        past the largest published Id)."""
+        if n_ids is None:
+            n_ids = max([-1] + list(by_id)) + 1
+        pt = PathTable(codec, max(len(by_path), 1), max(sum(len(p) for p in by_path), 1))
+        if by_path:
+            items = list(by_path.items())
+            pt.insert([p for p, _ in items], [i for _, i in items])
+        slot_of_id = np.full(n_ids, NO_SLOT, np.uint32)
+        rows, kids, heap = [], [], bytearray()
+        for slot, (i, v) in enumerate(sorted(by_id.items())):
+            if i < n_ids:
+                slot_of_id[i] = slot
+            rows.append(_flatten_value(v, kids, heap))
+        col = lambda a, k: [x[k] for x in a]
+        pub = PubTable(slot_of_id, [0] * (len(rows) + 1), [], 0, col(rows, 0), col(rows, 1),
+                       col(rows, 2), np.frombuffer(bytes(heap) or b"\0", np.uint8), device,
+                       cur_ctag=col(kids, 0) or [0], cur_cfixed=col(kids, 1) or [0],
+                       cur_caux=col(kids, 2) or [0])
+        allow = None
+        if denied_ids is not None:
+            allow = np.ones(n_ids, np.uint8)
+            for i in denied_ids:
+                if i < n_ids:
+                    allow[i] = 0
+        mv = max([9] + [_value_len(v) for v in by_id.values()])
+        return cls(pt, pub, allow, defaults, deferred_room, mv, device)
+
+    def c_struct(self):
+        self._pub = self.pub.c_struct()  # (kept alive: the C struct points at it)
+        def p(x):
+            return x.data_ptr() if x is not None and x.numel() else None
+        return NxgSubscribeTable(self.paths.h, C.addressof(self._pub), p(self.allow_of_id),
+                                 self.n_defaults, p(self.default_heap), p(self.default_off),
+                                 self.deferred_room)
+
+
+class SubscribeRoute:
+    """What Codec.route_subscribes returns (include/nxg_codec.h NxgSubscribeRoute): device tensors
+    outcome / span_id (per span of the columns), sub_id / sub_perm, deferred and reply, with the
+    counts in `s`."""
+
+    def __init__(self):
+        self.s = NxgSubscribeRoute()
+        self.ctl_begin = 0
+
+    def __getattr__(self, k):
+        s = self.__dict__.get("s")
+        if s is not None and k in ("n_spans", "n_sub", "n_deferred", "n_replies", "reply_len",
+                                   "next_ctl", "stopped"):
+            return int(getattr(s, k))
+        raise AttributeError(k)
+
+    @property
+    def n_outcome(self):
+        return [int(x) for x in self.s.n_outcome]
+
+    def numpy(self):
+        """Host copies, trimmed: outcome and span_id of the run's spans [ctl_begin, next_ctl), the
+        subscribed (id, permissions) pairs, the deferred span indices and the reply bytes."""
+        u = lambda t, n: t[:n].cpu().numpy().view(np.uint64)
+        n_sub = min(self.n_sub, self.sub_id.numel())
+        n_def = min(self.n_deferred, self.deferred.numel())
+        return {"outcome": self.outcome[self.ctl_begin:self.next_ctl].cpu().numpy().tolist(),
+                "span_id": self.span_id[self.ctl_begin:self.next_ctl].cpu().numpy()
+                .view(np.uint64).tolist(),
+                "sub": list(zip(u(self.sub_id, n_sub).tolist(),
+                                self.sub_perm[:n_sub].cpu().numpy().view(np.uint32).tolist())),
+                "deferred": u(self.deferred, n_def).tolist(),
+                "reply": self.reply[:min(self.reply_len, self.reply.numel())].cpu().numpy()
+                .tobytes()}
 
 
 def _heap_ptr(heap):

@@ -34,6 +34,7 @@
 // The control spans are pre-encoded Subscribe / Unsubscribe messages. No frame-cut bookkeeping
 // (note_split): the host refuses a write batch longer than MAX_BATCH.
 #include "nxg_device.h"
+#include "nxg_value_enc.h"
 
 #ifndef NXG_ENC_SKIP
 #define NXG_ENC_SKIP 0  // timing experiments only
@@ -75,6 +76,9 @@ __device__ unsigned long long nxg_enc_st[7][16384];
 
 namespace {
 
+// the Value sizing and emit walks (Slot, scalar_len / value_len, scalar_write / value_write)
+using namespace nxgenc;
+
 constexpr int TPB = 256;
 #ifndef NXG_ENC_GRPT
 #define NXG_ENC_GRPT 4
@@ -88,40 +92,6 @@ constexpr int TPB = 256;
 constexpr int GRPT = NXG_ENC_GRPT;       // rows per thread
 constexpr int GTILE = TPB * GRPT;        // rows per tile
 constexpr int GSTG = GTILE * NXG_ENC_BPR + 32;  // staging (config 3 averages 21.5 bytes per row)
-constexpr uint64_t kMaxVec = 2ull * 1024 * 1024 * 1024;
-
-struct Slot {
-    uint32_t tag;
-    uint64_t fixed;
-    uint32_t aux;
-};
-
-NXG_DEV Slot get_slot(const ColsDesc& c, bool row, uint64_t i) {
-    if (row) return Slot{c.tag[i], c.fixed[i], c.aux[i]};
-    return Slot{c.ctag[i], c.cfixed[i], c.caux[i]};
-}
-
-NXG_DEV bool is_container(uint32_t tag) { return tag == 19 || tag == 21 || tag == 22; }
-
-// |Value| of a non-container value (tags other than 19, 21, 22); 0 => unknown tag
-NXG_DEV uint64_t scalar_len(const Slot& s) {
-    switch (s.tag) {
-    case 0: case 2: case 8: return 5;
-    case 1: return 1 + vl64((uint32_t)s.fixed);
-    case 3: return 1 + vl64(zz32((int32_t)(uint32_t)s.fixed));
-    case 4: case 6: case 9: return 9;
-    case 5: return 1 + vl64(s.fixed);
-    case 7: return 1 + vl64(zz64((int64_t)s.fixed));
-    case 10: case 11: return 13;
-    case 12: case 13: case 18: return 1 + vl64(s.aux) + s.aux;
-    case 14: case 15: case 16: return 1;
-    case 20: return 17;
-    case 23: case 24: return 2;
-    case 25: case 26: return 3;
-    case 27: return 1 + lwlen(s.aux);
-    default: return 0;
-    }
-}
 
 #ifndef NXG_ENC_AFAST
 #define NXG_ENC_AFAST 1  // arrays of 1..8 fixed-size elements sized from one load of their tags (the same on the write side: no gain)
@@ -143,72 +113,6 @@ NXG_DEV uint64_t tags8(const uint8_t* p, uint32_t n) {
     const uint64_t v = (uint64_t)__builtin_amdgcn_alignbyte(w1, w0, sh) |
                        ((uint64_t)__builtin_amdgcn_alignbyte(w2, w1, sh) << 32);
     return n >= 8 ? v : v & ((1ull << (8 * n)) - 1ull);
-}
-
-// The general walk's stack: kStk levels of (children left, next child slot), in LDS, one stack
-// per wave (the walk runs one lane at a time: one_lane_at_a_time). Kept out of registers and
-// scratch: a dynamically indexed private array would be scratch memory in every wave.
-constexpr int kStk = NXG_MAX_DEPTH + 2;
-struct WalkStack {
-    uint64_t rem[kStk];
-    uint64_t slot[kStk];
-};
-
-// |Value| for the value in (row?, slot), children included; 0 => error (*err set)
-NXG_DEV uint64_t value_len(const ColsDesc& c, bool row, uint64_t slot, uint32_t* err,
-                           WalkStack* stk) {
-    uint64_t* frem = stk->rem;
-    uint64_t* fslot = stk->slot;
-    int top = -1, depth = 0;
-    bool is_row = row;
-    uint64_t cur = slot, total = 0;
-    for (;;) {
-        if (depth > NXG_MAX_DEPTH) {
-            *err = 6;
-            return 0;
-        }
-        const Slot s = get_slot(c, is_row, cur);
-        uint64_t kids = 0;
-        switch (s.tag) {
-        case 0: case 2: case 8: total += 5; break;
-        case 1: total += 1 + vl64((uint32_t)s.fixed); break;
-        case 3: total += 1 + vl64(zz32((int32_t)(uint32_t)s.fixed)); break;
-        case 4: case 6: case 9: total += 9; break;
-        case 5: total += 1 + vl64(s.fixed); break;
-        case 7: total += 1 + vl64(zz64((int64_t)s.fixed)); break;
-        case 10: case 11: total += 13; break;
-        case 12: case 13: case 18: total += 1 + vl64(s.aux) + s.aux; break;
-        case 14: case 15: case 16: total += 1; break;
-        case 19:
-        case 21:
-            if ((uint64_t)s.aux * (s.tag == 19 ? 16 : 32) > kMaxVec) {  // encode guard
-                *err = 2;
-                return 0;
-            }
-            total += 1 + vl64(s.aux);
-            kids = s.tag == 19 ? s.aux : 2ull * s.aux;
-            break;
-        case 20: total += 17; break;
-        case 22: total += 1; kids = 1; break;
-        case 23: case 24: total += 2; break;
-        case 25: case 26: total += 3; break;
-        case 27: total += 1 + lwlen(s.aux); break;
-        default:
-            *err = 1;
-            return 0;
-        }
-        if (kids) {
-            ++top;
-            frem[top] = kids;
-            fslot[top] = s.fixed;
-        }
-        while (top >= 0 && frem[top] == 0) top--;
-        if (top < 0) return total;
-        frem[top]--;
-        cur = fslot[top]++;
-        is_row = false;
-        depth = top + 1;
-    }
 }
 
 struct Out {
@@ -251,72 +155,6 @@ struct Out {
         for (uint64_t i = 0; i < n; i++) o[p++] = src[i];
     }
 };
-
-template <typename W>
-NXG_DEV void value_write(const ColsDesc& c, const uint8_t* heap, bool row, uint64_t slot, W& w,
-                         WalkStack* stk) {
-    uint64_t* frem = stk->rem;
-    uint64_t* fslot = stk->slot;
-    int top = -1;
-    bool is_row = row;
-    uint64_t cur = slot;
-    for (;;) {
-        const Slot s = get_slot(c, is_row, cur);
-        uint64_t kids = 0;
-        w.b(s.tag);
-        switch (s.tag) {
-        case 0: case 2: case 8: w.be(s.fixed, 4); break;
-        case 1: w.var((uint32_t)s.fixed); break;
-        case 3: w.var(zz32((int32_t)(uint32_t)s.fixed)); break;
-        case 4: case 6: case 9: w.be(s.fixed, 8); break;
-        case 5: w.var(s.fixed); break;
-        case 7: w.var(zz64((int64_t)s.fixed)); break;
-        case 10: case 11: w.be(s.fixed, 8); w.be(s.aux, 4); break;
-        case 12: case 13: case 18: w.var(s.aux); w.copy(heap + s.fixed, s.aux); break;
-        case 19: case 21:
-            w.var(s.aux);
-            kids = s.tag == 19 ? s.aux : 2ull * s.aux;
-            break;
-        case 20: w.copy(heap + s.fixed, 16); break;
-        case 22: kids = 1; break;
-        case 23: case 24: w.be(s.fixed, 1); break;
-        case 25: case 26: w.be(s.fixed, 2); break;
-        case 27: w.var(lwlen(s.aux)); w.copy(heap + s.fixed, s.aux); break;
-        default: break;
-        }
-        if (kids) {
-            ++top;
-            frem[top] = kids;
-            fslot[top] = s.fixed;
-        }
-        while (top >= 0 && frem[top] == 0) top--;
-        if (top < 0) return;
-        frem[top]--;
-        cur = fslot[top]++;
-        is_row = false;
-    }
-}
-
-// Writes a non-container value (tag byte included).
-template <typename W>
-NXG_DEV void scalar_write(const Slot& s, const uint8_t* heap, W& w) {
-    w.b(s.tag);
-    switch (s.tag) {
-    case 0: case 2: case 8: w.be(s.fixed, 4); break;
-    case 1: w.var((uint32_t)s.fixed); break;
-    case 3: w.var(zz32((int32_t)(uint32_t)s.fixed)); break;
-    case 4: case 6: case 9: w.be(s.fixed, 8); break;
-    case 5: w.var(s.fixed); break;
-    case 7: w.var(zz64((int64_t)s.fixed)); break;
-    case 10: case 11: w.be(s.fixed, 8); w.be(s.aux, 4); break;
-    case 12: case 13: case 18: w.var(s.aux); w.copy(heap + s.fixed, s.aux); break;
-    case 20: w.copy(heap + s.fixed, 16); break;
-    case 23: case 24: w.be(s.fixed, 1); break;
-    case 25: case 26: w.be(s.fixed, 2); break;
-    case 27: w.var(lwlen(s.aux)); w.copy(heap + s.fixed, s.aux); break;
-    default: break;
-    }
-}
 
 // Row r's |Value| without the stack when the value is a scalar, text, or an array whose
 // elements are not containers; `flat` false (and 0) otherwise, or on an unknown tag.

@@ -436,3 +436,96 @@ struct ColsDesc {
     uint8_t* wflags;
     uint64_t* wid;
 };
+
+// the path table and Subscribe routing (nxg_route_subscribes.hip)
+// A path table as the kernels see it: open addressing, linear probing from hash & mask. A slot's
+// hash word is 0 (empty: a probe ends here), 1 (tombstone: probed past, reused by inserts) or the
+// key's 64-bit hash (>= 2); a hit is a hash match confirmed by all of the key's bytes.
+struct NxgPtView {
+    uint64_t* hash;     // [mask + 1]
+    uint64_t* key_off;  // [mask + 1]: the key's bytes at heap + key_off
+    uint32_t* key_len;
+    uint64_t* id;
+    uint8_t* heap;      // the table's own copy of the inserted paths (16 readable bytes past it)
+    uint64_t mask;      // slots - 1 (slots: a power of two, >= 2 * cap_paths)
+};
+struct NxgPtHead {  // device, zeroed per call, copied back after the last launch
+    uint64_t n_dup;      // insert: paths that lost (already present, or a lower index of the call)
+    uint64_t n_missing;  // remove: paths not found
+    uint64_t n_fresh;    // insert: empty slots taken (tombstones reused are not counted)
+    uint64_t pad;
+};
+// insert: path i is heap[heap_base + off[i] .. heap_base + off[i + 1]) (already copied there).
+// hash pass (the hash, and whether the table has the path), claim pass (the call's equal paths
+// meet in a scratch table `tmp` of tmp_mask + 1 words preset to ~0: atomicMin keeps the lowest
+// index), place pass (the winners into the table). `h`: n words, `tslot`: n words, `state`: n bytes.
+hipError_t nxg_launch_pt_insert(const NxgPtView& t, uint64_t heap_base, const uint64_t* off,
+                                const uint64_t* id, uint64_t n, uint64_t* h, uint64_t* tmp,
+                                uint64_t tmp_mask, uint64_t* tslot, uint8_t* state,
+                                NxgPtHead* head, hipStream_t s);
+// remove: path i is keys[off[i] .. off[i + 1]) (device staging, 16 readable bytes past it)
+hipError_t nxg_launch_pt_remove(const NxgPtView& t, const uint8_t* keys, const uint64_t* off,
+                                uint64_t n, NxgPtHead* head, hipStream_t s);
+hipError_t nxg_launch_pt_lookup(const NxgPtView& t, const uint8_t* heap, const uint64_t* off,
+                                const uint32_t* len, uint64_t n, uint64_t* id_out, hipStream_t s);
+// every live entry of `from` into `to` (empty, at least as many slots): drops the tombstones
+hipError_t nxg_launch_pt_rehash(const NxgPtView& from, const NxgPtView& to, hipStream_t s);
+
+struct NxgRsHead {  // device, zeroed per call, copied back whole after the last launch
+    uint64_t stop_inv;   // ~k of the first span k >= ctl_begin that ends the run (atomicMax; 0: none)
+    uint64_t bad_inv;    // ~k of the first span whose current value cannot be encoded (0: none)
+    uint32_t bad_kind, pad0;
+    uint64_t reply_bytes;
+    uint64_t n_replies, n_sub;
+    uint64_t n_outcome[5];
+    uint64_t next_ctl;
+    uint32_t stopped, pad1;
+    uint64_t pad[3];
+};
+static_assert(sizeof(NxgRsHead) == 128, "NxgRsHead layout");
+struct NxgRsArgs {
+    NxgPtView paths;
+    ColsDesc cur;  // the published values: tag / fixed / aux by slot, the children; null tag: F64
+    const uint8_t* cur_heap;
+    uint64_t n_ids, n_slots;
+    const uint32_t* slot_of_id;
+    const uint8_t* allow_of_id;
+    uint64_t n_defaults;
+    const uint8_t* default_heap;
+    const uint64_t* default_off;
+    uint64_t deferred_room;
+    const uint8_t* frame;
+    const uint64_t* ctl_row;
+    const uint64_t* ctl_off;
+    const uint32_t* ctl_len;
+    const uint8_t* ctl_variant;
+    const uint32_t* span_perm;
+    uint64_t n_ctl, row_begin, ctl_begin;
+    // outputs
+    uint8_t* outcome;
+    uint64_t* span_id;
+    uint64_t* sub_id;
+    uint32_t* sub_perm;
+    uint64_t cap_sub;
+    uint64_t* deferred;
+    uint64_t cap_deferred;
+    uint8_t* reply;
+    uint64_t cap_reply;
+    // scratch, placed by the launcher (per span from ctl_begin / per block of kRwBlock spans)
+    NxgRsHead* head;
+    uint64_t* poff;   // the path's first byte in the frame
+    uint64_t* vlen;   // |Value| of the current value (Subscribed spans)
+    uint64_t* zloc;   // reply bytes before the span within its block
+    uint64_t* sid;    // the Id its path resolves to, or NXG_NO_ID
+    uint32_t* plen;
+    uint32_t* cloc;   // deferral candidates before the span within its block
+    uint32_t* sloc;   // Subscribed spans before it within its block
+    uint8_t* pre;     // the resolve pass's verdict (an NxgSubscribeOutcome, or kRsCandidate)
+    uint64_t* cblk;   // per block: deferral candidates
+    uint64_t* zblk;   // per block: reply bytes
+    uint64_t* nblk;   // per block: replies | Subscribed << 32
+    uint64_t* oblk;   // per block, three arrays: outcomes 0 | 1 << 32, 2 | 3 << 32, 4
+};
+uint64_t nxg_rs_scratch_bytes(uint64_t spans);
+// a.head is at `scratch` afterwards; `scratch` needs no initialising
+hipError_t nxg_launch_route_subscribes(NxgRsArgs a, uint8_t* scratch, hipStream_t s);
