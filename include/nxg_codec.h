@@ -560,6 +560,13 @@ bool nxg_path_table_lookup(NxgCtx* ctx, const NxgPathTable* t, const uint8_t* dh
  * splitting honours `\` escapes; a plain path is canonical as it stands, so its wire bytes are
  * the by_path key. Host-side, no ctx. */
 bool nxg_path_is_plain(const uint8_t* path, uint64_t len);
+/* The 64-bit word the table stores for a path, computed on the host exactly as the kernels compute
+ * it: a multiplicative hash over the path's length and its little-endian 8-byte words (the last
+ * one zero above the path's end), never 0 or 1 (those mark empty slots and tombstones: a raw 0 or
+ * 1 is stored as 2 or 3). A path's probe starts at slot hash & (slots - 1). The seam that tests
+ * and tools check their own statement of the hash against; distinct paths can share a hash, and
+ * the table then tells them apart by their bytes. Host-side, no ctx. */
+uint64_t nxg_path_hash(const uint8_t* path, uint64_t len);
 
 /* ---- Subscribe routing: replaces the Subscribe arm of ClientCtx::handle_batch_inner
  * (netidx/src/publisher/server.rs:506-549) and subscribe() (server.rs:60-137) -----------------
@@ -653,10 +660,16 @@ typedef struct NxgSubscribeRoute {
  * (server.rs:244-271) and passes the permission bits, or NXG_SUB_PERM_DENY for "no stored secret"
  * and "token invalid" alike. One synchronisation; synchronous. Returns false on misuse (the
  * message names the field: host or F64-layout columns, a missing array, ctl_begin > n_ctl, a
- * pointer that is not device memory), on a HIP failure, when a current value cannot be encoded
- * (an unknown tag, nesting past NXG_MAX_DEPTH), or when a capacity is exceeded (NXG_CAPACITY in
- * the message); the counts then hold the required values (n_sub, n_deferred, reply_len) and the
- * arrays hold what fitted, as nxg_route_writes does. */
+ * pointer that is not device memory), on a HIP failure, when the current value of a Subscribed
+ * span of the run cannot be encoded, or when a capacity is exceeded (NXG_CAPACITY in the message);
+ * the counts then hold the required values (n_sub, n_deferred, reply_len) and the arrays hold what
+ * fitted, as nxg_route_writes does. A value cannot be encoded when it or an element has an unknown
+ * tag, when a container has no child columns or more elements than MAX_VEC allows, or when it
+ * nests deeper than nxg_encode_updates accepts: the root is level 0, and a value at a level past
+ * NXG_MAX_DEPTH is refused (NXG_MAX_DEPTH containers around a scalar are the deepest). The message
+ * names the lowest such span and that span's cause, whatever the scheduling. A value nobody is
+ * answered with (behind the stop, or under an Id that is denied, not in by_id or not asked for)
+ * is not looked at. */
 bool nxg_route_subscribes(NxgCtx* ctx, const NxgSubscribeTable* tab, const uint8_t* frame,
                           const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
                           const uint32_t* span_perm, NxgSubscribeRoute* out, NetidxError* err);

@@ -17,7 +17,7 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     WindowCapacity, WriteTable, WriteRoute, RouteCapacity, NOT_SUBSCRIBED,
                     PERM_WRITE, WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED,
                     WRITE_NOT_ACCEPTED, PathTable, SubscribeTable, SubscribeRoute, path_is_plain,
-                    NO_ID, SUB_PERM_DENY, PERM_ALL, SUB_SUBSCRIBED, SUB_NO_SUCH_VALUE, SUB_DENIED,
+                    path_hash, NO_ID, SUB_PERM_DENY, PERM_ALL, SUB_SUBSCRIBED, SUB_NO_SUCH_VALUE, SUB_DENIED,
                     SUB_DEFERRED, SUB_IGNORED, MAX_DEFERRED)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
@@ -31,6 +31,6 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "WRITE_NO_WID", "PATH_WRITES", "ArchiveImage", "WindowCapacity", "WriteTable",
            "WriteRoute", "RouteCapacity", "NOT_SUBSCRIBED", "PERM_WRITE", "WRITE_ROUTED",
            "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED", "PathTable",
-           "SubscribeTable", "SubscribeRoute", "path_is_plain", "NO_ID", "SUB_PERM_DENY",
+           "SubscribeTable", "SubscribeRoute", "path_is_plain", "path_hash", "NO_ID", "SUB_PERM_DENY",
            "PERM_ALL", "SUB_SUBSCRIBED", "SUB_NO_SUCH_VALUE", "SUB_DENIED", "SUB_DEFERRED",
            "SUB_IGNORED", "MAX_DEFERRED"]

@@ -270,6 +270,7 @@ SIGNATURES = {
                                          C.c_void_p, C.c_uint64, C.c_void_p,
                                          C.POINTER(NetidxError)]),
     "nxg_path_is_plain": (C.c_bool, [C.c_void_p, C.c_uint64]),
+    "nxg_path_hash": (C.c_uint64, [C.c_void_p, C.c_uint64]),
     "nxg_route_subscribes": (C.c_bool, [C.c_void_p, C.POINTER(NxgSubscribeTable), C.c_void_p,
                                         C.POINTER(NxgColumns), C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.POINTER(NxgSubscribeRoute),
@@ -1382,6 +1383,14 @@ def path_is_plain(path):
     p = path.encode() if isinstance(path, str) else bytes(path)
     b = (C.c_uint8 * max(len(p), 1)).from_buffer_copy(p + b"\0")
     return bool(lib().nxg_path_is_plain(b, len(p)))
+
+
+def path_hash(path, offset=0):
+    """nxg_path_hash: the word a PathTable stores for the path (never 0 or 1). `offset` places
+    the bytes that many bytes into the buffer handed over (the answer does not depend on it)."""
+    p = path.encode() if isinstance(path, str) else bytes(path)
+    b = (C.c_uint8 * (offset + len(p) + 1)).from_buffer_copy(b"\xa5" * offset + p + b"\xa5")
+    return int(lib().nxg_path_hash(C.addressof(b) + offset, len(p)))
 
 
 def _pack_paths(paths):

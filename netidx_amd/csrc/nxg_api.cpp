@@ -16,6 +16,7 @@
 
 #include "../../include/nxg_codec.h"
 #include "nxg_internal.h"
+#include "nxg_path_hash.h"
 
 namespace {
 
@@ -3289,6 +3290,16 @@ bool nxg_path_is_plain(const uint8_t* p, uint64_t len) {
     return p[len - 1] != '/' || len == 1;
 }
 
+uint64_t nxg_path_hash(const uint8_t* p, uint64_t len) {
+    uint64_t h = nxgpath::kSeed ^ len;
+    for (uint64_t i = 0; p && i < len; i += 8) {
+        uint64_t w = 0;  // the little-endian word of bytes i .. i + 8, zero past the end
+        for (uint64_t b = 0; b < 8 && i + b < len; b++) w |= (uint64_t)p[i + b] << (8 * b);
+        h = nxgpath::mix(h, w);
+    }
+    return nxgpath::finish_hash(h);
+}
+
 bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t* frame,
                           const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
                           const uint32_t* span_perm, NxgSubscribeRoute* out, NetidxError* err) {
@@ -3454,12 +3465,14 @@ bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t
     for (int o = 0; o < 5; o++) out->n_outcome[o] = h.n_outcome[o];
     out->next_ctl = h.next_ctl;
     out->stopped = h.stopped;
-    if (h.bad_inv && ~h.bad_inv < h.next_ctl) {
+    // (a span behind the final stop was resolved before a path in front of it lowered the stop)
+    const uint64_t bad_k = ~(h.bad_inv >> 8 | 0xffull << 56), bad_kind = h.bad_inv & 0xff;
+    if (h.bad_inv && bad_k < h.next_ctl) {
         set_err(err, "tab->pub: the current value of span %llu's Id cannot be encoded (%s)",
-                (unsigned long long)~h.bad_inv,
-                h.bad_kind == 6 ? "nested deeper than NXG_MAX_DEPTH"
-                : h.bad_kind == 2 ? "a container past MAX_VEC, or no child columns"
-                                  : "unknown tag");
+                (unsigned long long)bad_k,
+                bad_kind == 6   ? "nested deeper than NXG_MAX_DEPTH"
+                : bad_kind == 2 ? "a container past MAX_VEC, or no child columns"
+                                : "unknown tag");
         return false;
     }
     if (out->n_sub > out->cap_sub || out->n_deferred > out->cap_deferred ||

@@ -473,8 +473,9 @@ hipError_t nxg_launch_pt_rehash(const NxgPtView& from, const NxgPtView& to, hipS
 
 struct NxgRsHead {  // device, zeroed per call, copied back whole after the last launch
     uint64_t stop_inv;   // ~k of the first span k >= ctl_begin that ends the run (atomicMax; 0: none)
-    uint64_t bad_inv;    // ~k of the first span whose current value cannot be encoded (0: none)
-    uint32_t bad_kind, pad0;
+    uint64_t bad_inv;    // ~k << 8 | cause, of the first span k whose current value cannot be
+                         // encoded (atomicMax: one word, so the cause is that span's; 0: none)
+    uint64_t pad0;
     uint64_t reply_bytes;
     uint64_t n_replies, n_sub;
     uint64_t n_outcome[5];

@@ -51,6 +51,7 @@
 
 #include "nxg_device.h"
 #include "nxg_internal.h"
+#include "nxg_path_hash.h"
 #include "nxg_value_enc.h"
 
 namespace {
@@ -108,20 +109,12 @@ NXG_DEV uint64_t eq_bytes(uint64_t x, uint8_t c) {
     return ~(((x & k7) + k7) | x | k7);
 }
 
-NXG_DEV uint64_t mix(uint64_t h, uint64_t w) {
-    h = (h ^ w) * 0x9E3779B97F4A7C15ull;
-    return h ^ (h >> 29);
-}
-NXG_DEV uint64_t finish_hash(uint64_t h) {
-    h ^= h >> 32;
-    h *= 0xD6E8FEB86659FD93ull;
-    h ^= h >> 29;
-    return h < 2 ? h + 2 : h;  // 0 and 1 mark empty slots and tombstones
-}
-// the hash of path bytes [p, p + len), and whether the path is plain
+using nxgpath::finish_hash;
+using nxgpath::mix;
+// the hash of path bytes [p, p + len) (nxg_path_hash.h), and whether the path is plain
 template <typename S>
 NXG_DEV uint64_t path_hash(const S& s, uint64_t p, uint32_t len, bool* plain) {
-    uint64_t h = 0x243F6A8885A308D3ull ^ len;
+    uint64_t h = nxgpath::kSeed ^ len;
     uint64_t bad = 0, prev_slash = 0, w = 0;
     for (uint32_t i = 0; i < len; i += 8) {
         w = s.word(p + i, len - i < 8 ? len - i : 8);
@@ -461,8 +454,8 @@ NXG_DEV void rs_resolve(const NxgRsArgs& a, const S& src, uint64_t s0, uint64_t*
             }
         }
     }
-    // containers: the root here, each element's subtree by the shared walk (one lane at a time on
-    // the wave's LDS stack)
+    // containers: the root here (level 0, as the encoder counts it), each element's subtree by the
+    // shared walk from level 1 (one lane at a time on the wave's LDS stack)
     uint32_t err = 0;
     one_lane_at_a_time(walk, [&] {
         if (!a.cur.ctag || (v.tag != 22 && (uint64_t)v.aux * (v.tag == 19 ? 16 : 32) > kMaxVec)) {
@@ -472,12 +465,13 @@ NXG_DEV void rs_resolve(const NxgRsArgs& a, const S& src, uint64_t s0, uint64_t*
         vlen = 1 + (v.tag == 22 ? 0 : vl64(v.aux));
         const uint64_t nk = kids_of(v);
         for (uint64_t c = 0; c < nk && !err; c++)
-            vlen += value_len(a.cur, false, v.fixed + c, &err, stk);
+            vlen += value_len(a.cur, false, v.fixed + c, &err, stk, 1);
     });
     if (live && pre == NXG_SUB_SUBSCRIBED && (err || !vlen)) {
         vlen = 0;
-        if (atomicMax((unsigned long long*)&a.head->bad_inv, (unsigned long long)~k) < ~k)
-            a.head->bad_kind = err ? err : 1;
+        // the lowest such span wins, and its cause travels in the same word (k < 2^56)
+        atomicMax((unsigned long long*)&a.head->bad_inv,
+                  (unsigned long long)(~k << 8 | (err ? err : 1u)));
     }
     if (live) {
         a.pre[j] = pre;

@@ -56,12 +56,15 @@ struct WalkStack {
     uint64_t slot[kStk];
 };
 
-// |Value| for the value in (row?, slot), children included; 0 => error (*err set)
+// |Value| for the value in (row?, slot), children included; 0 => error (*err set). The value is
+// at nesting level `level` of the Value it belongs to (0: it is the root; a caller that sizes a
+// container's root itself walks the elements from level 1): a value at a level past
+// NXG_MAX_DEPTH is error 6, so the stack holds at most NXG_MAX_DEPTH + 1 - level frames.
 NXG_DEV uint64_t value_len(const ColsDesc& c, bool row, uint64_t slot, uint32_t* err,
-                           WalkStack* stk) {
+                           WalkStack* stk, int level = 0) {
     uint64_t* frem = stk->rem;
     uint64_t* fslot = stk->slot;
-    int top = -1, depth = 0;
+    int top = -1, depth = level;
     bool is_row = row;
     uint64_t cur = slot, total = 0;
     for (;;) {
@@ -109,7 +112,7 @@ NXG_DEV uint64_t value_len(const ColsDesc& c, bool row, uint64_t slot, uint32_t*
         frem[top]--;
         cur = fslot[top]++;
         is_row = false;
-        depth = top + 1;
+        depth = level + top + 1;
     }
 }
 

@@ -96,9 +96,12 @@ def perms_of(items):
     return [m[2] if m[0] == "sub" and m[2] is not None else sm.ALL for m in spans]
 
 
-def check_run(codec, st0, items, ctl_begin=0, row_begin=0, n_ids=None, want_stop=None):
-    """One call over the run that starts at span ctl_begin, against the model."""
-    frame, cols, _ = decode(codec, items)
+def check_run(codec, st0, items, ctl_begin=0, row_begin=0, n_ids=None, want_stop=None, tab=None,
+              decoded=None):
+    """One call over the run that starts at span ctl_begin, against the model. tab: a
+    SubscribeTable that holds st0 (default: one built fresh from it); decoded: what decode()
+    returned for these items (default: decoded here)."""
+    frame, cols, _ = decoded if decoded is not None else decode(codec, items)
     spans, rows = [], 0  # (message, rows in front of it) per control span
     for m in items:
         if m[0] == "w":
@@ -113,7 +116,8 @@ def check_run(codec, st0, items, ctl_begin=0, row_begin=0, n_ids=None, want_stop
         run.append(m[1])
     st = st0.copy()
     want, n = sm.route(st, run, perm, ctl_begin)
-    r = codec.route_subscribes(table_of(codec, st0, n_ids), frame, cols, row_begin, ctl_begin, perm)
+    r = codec.route_subscribes(tab if tab is not None else table_of(codec, st0, n_ids), frame, cols,
+                               row_begin, ctl_begin, perm)
     h = r.numpy()
     assert r.next_ctl == ctl_begin + n and r.n_spans == n
     assert h["outcome"] == want.outcome
