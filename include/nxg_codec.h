@@ -256,6 +256,42 @@ void nxg_write_cols_free(NxgCtx* ctx, NxgWriteCols* cols);
  * false on misuse, a HIP failure or an exceeded capacity (NXG_CAPACITY in the message). */
 bool nxg_decode_writes(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColumns* out,
                        NxgWriteCols* wout, NxgStatus* st, NetidxError* err);
+/* The same call with options; opts NULL (or fast = 0) is nxg_decode_writes itself: the same
+ * launches, path 6, the same errors. fast = 1 tries the tile-parallel fast decoder first, under
+ * the argument and capacity contract of nxg_decode_writes word for word (device or pinned-host
+ * columns, host or device frame, NXG_CAPACITY with the same message and zeroed counts, nothing at
+ * or past any capacity written, a malformed frame true with (err_kind, err_offset) and zero counts,
+ * synchronous only). The fast decoder takes a frame whose every message is, with its length
+ * filled exactly and a canonical length prefix (L counts its own prefix),
+ *   a Write `L 02 varint(id) bool Value [varint(wid)]` of a one-byte L, an id of any width,
+ *     bool 0 or 1, a valid Value without child slots (fixed-size and varint scalars,
+ *     DateTime, Duration, String, Bytes, Decimal, Error(String)), and then nothing
+ *     (NXG_WRITE_NO_WID) or one varint of 1-10 bytes,
+ *   an Unsubscribe `L 01 varint(id)`, or
+ *   a Subscribe `varint(L) 00 varint(plen) path tag addr u64 u32 varint(tlen) token` with address
+ *     tag 0 or 1, canonical plen / tlen, a UTF-8 path, and at most 256 bytes in all (prefix
+ *     included).
+ * Non-canonical id / wid varints are taken too. It declines everything else -- Subscribes
+ * longer than 256 bytes, non-canonical plen / tlen, Array / Map / Error(Value) / Abstract values,
+ * bytes left inside a length wrap (a wid cut short by the message end included), every frame the
+ * general decoder rejects, frames of 4 GiB or more, and columns too small for the frame -- and
+ * the same call then reruns the frame on the general decoder. st->path (and the status
+ * nxg_last_status reports) is NXG_PATH_WRITES_FAST when the fast decoder took the frame, which
+ * implies err_kind 0 and n_children 0, and NXG_PATH_WRITES after a decline; the columns are
+ * identical either way. A frame of the accepted set can still fall back for a geometric reason
+ * (bytes inside values or tokens that spell a chain of messages which crosses a 4 KiB tile edge
+ * without rejoining the true one, or more than 16 such false chains in front of the first true
+ * message start of each of two adjacent tiles). A decline keeps no state: the next call tries the fast decoder again. An
+ * empty frame launches nothing and reports path 6. fast > 1 or reserved != 0 is misuse (false,
+ * with a message, before any use of the context). */
+#define NXG_PATH_WRITES_FAST 8 /* NxgStatus.path: the fast To decoder took the frame */
+typedef struct NxgWriteDecodeOpts {
+    uint32_t fast;     /* 0: the general decoder only (nxg_decode_writes); 1: try the fast decoder first */
+    uint32_t reserved; /* must be 0 */
+} NxgWriteDecodeOpts;
+bool nxg_decode_writes_opts(NxgCtx* ctx, const uint8_t* frame, uint64_t len, NxgColumns* out,
+                            NxgWriteCols* wout, const NxgWriteDecodeOpts* opts /* NULL = defaults */,
+                            NxgStatus* st, NetidxError* err);
 /* Each row becomes varint(L) 02 varint(id) (wflags & NXG_WRITE_REPLY) Value varint(wid), with
  * L = lw(1 + vl(id) + 1 + |Value| + vl(wid)); NXG_WRITE_NO_WID is ignored (the reference encoder
  * always writes the WriteId). Control spans (pre-encoded Subscribe / Unsubscribe messages) are

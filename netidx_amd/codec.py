@@ -35,6 +35,7 @@ HINT_MIXED = 1
 # To frames (nxg_decode_writes): NxgWriteFlags and the status path
 WRITE_REPLY, WRITE_NO_WID = 1, 2
 PATH_WRITES = 6
+PATH_WRITES_FAST = 8  # the fast To decoder took the frame (decode_writes(fast=True))
 
 
 class PackError(Exception):
@@ -73,6 +74,10 @@ class NxgColumns(C.Structure):
 class NxgWriteCols(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("pad", C.c_uint32), ("cap_rows", C.c_uint64),
                 ("wflags", C.c_void_p), ("wid", C.c_void_p)]
+
+
+class NxgWriteDecodeOpts(C.Structure):
+    _fields_ = [("fast", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class NxgRange(C.Structure):
@@ -246,6 +251,10 @@ SIGNATURES = {
     "nxg_decode_writes": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(NxgColumns),
                                      C.POINTER(NxgWriteCols), C.POINTER(NxgStatus),
                                      C.POINTER(NetidxError)]),
+    "nxg_decode_writes_opts": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64,
+                                          C.POINTER(NxgColumns), C.POINTER(NxgWriteCols),
+                                          C.POINTER(NxgWriteDecodeOpts), C.POINTER(NxgStatus),
+                                          C.POINTER(NetidxError)]),
     "nxg_encoded_writes_len": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns),
                                           C.POINTER(NxgWriteCols), C.c_void_p,
                                           C.POINTER(C.c_uint64), C.POINTER(NetidxError)]),
@@ -946,11 +955,13 @@ class Codec:
         return out[:n]
 
     # ---- publisher::To: subscriber write batches ---------------------------------------------
-    def decode_writes(self, frame, cols=None, wcols=None, check=True):
+    def decode_writes(self, frame, cols=None, wcols=None, check=True, fast=False):
         """Decode one To frame (Subscribe / Unsubscribe / Write; host bytes or a device tensor):
         returns (Columns, WriteCols). Rows are the Writes, with wcols.wflags / wcols.wid; the
         other messages are control spans. A malformed frame raises PackError(kind, offset) (check);
-        last_status() and self.writes_status describe the decode."""
+        last_status() and self.writes_status describe the decode. fast: try the tile-parallel
+        fast decoder first (nxg_decode_writes_opts; path PATH_WRITES_FAST when it takes the
+        frame, PATH_WRITES after the fallback to the general decoder; the same columns)."""
         n = len(frame) if not hasattr(frame, "numel") else frame.numel()
         if cols is None:
             cols = Columns(n // 5 + 1, n + 1, n // 3 + 1, LAYOUT_MIXED,
@@ -959,8 +970,14 @@ class Codec:
             wcols = WriteCols(cols.caps["rows"], cols.device)
         ptr, keep = _frame_ptr(frame)
         st, err = NxgStatus(), NetidxError()
-        ok = lib().nxg_decode_writes(self.ctx, C.c_void_p(ptr), n, C.byref(cols.s),
-                                     C.byref(wcols.s), C.byref(st), C.byref(err))
+        if fast:
+            opts = NxgWriteDecodeOpts(1, 0)
+            ok = lib().nxg_decode_writes_opts(self.ctx, C.c_void_p(ptr), n, C.byref(cols.s),
+                                              C.byref(wcols.s), C.byref(opts), C.byref(st),
+                                              C.byref(err))
+        else:
+            ok = lib().nxg_decode_writes(self.ctx, C.c_void_p(ptr), n, C.byref(cols.s),
+                                         C.byref(wcols.s), C.byref(st), C.byref(err))
         _check(ok, err)
         self.writes_status = st
         if check and st.err_kind:

@@ -2734,10 +2734,24 @@ void nxg_write_cols_free(NxgCtx* c, NxgWriteCols* w) {
 // general decoder's To instantiation (nxg_decode_gen.hip), synchronously.
 bool nxg_decode_writes(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgColumns* out,
                        NxgWriteCols* wout, NxgStatus* ust, NetidxError* err) {
+    return nxg_decode_writes_opts(c, frame, len, out, wout, nullptr, ust, err);
+}
+
+// opts->fast: the fast To decoder (nxg_decode_writes_fast.hip) first; a frame it declines
+// (DevStatus.fast_fail) is rerun on the general decoder here, as finish_decode does for FAST_MIX.
+bool nxg_decode_writes_opts(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgColumns* out,
+                            NxgWriteCols* wout, const NxgWriteDecodeOpts* opts, NxgStatus* ust,
+                            NetidxError* err) {
     if (!c || !out || !wout || !ust || (!frame && len)) {
         set_err(err, "null argument");
         return false;
     }
+    if (opts && (opts->fast > 1u || opts->reserved != 0u)) {
+        set_err(err, "NxgWriteDecodeOpts: fast = %u (0 or 1), reserved = %u (must be 0)",
+                opts->fast, opts->reserved);
+        return false;
+    }
+    const bool try_fast = opts && opts->fast == 1u && nxg_wfast_takes(len);
     // (the argument checks come before any use of the context)
     if (!mixed_capable(out) || !out->id || !out->fixed) {
         set_err(err, "write batches decode into MIXED-layout columns");
@@ -2787,23 +2801,46 @@ bool nxg_decode_writes(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgColumns
     if (!frame_to_device(c, frame, len, &df, err)) return false;
     DevStatus* st;
     uint32_t slot;
-    if (!begin_call(c, &st, &slot, err)) return false;
-    bool ok = ensure_glws(c, nxg_dec_gen_scratch_bytes(len), err);
-    if (ok) {
-        const ColsDesc d = desc_of(target, &wtarget);
-        const hipError_t le =
-            nxg_launch_dec_gen(df, len, d, c->glws, c->gruns,
-                               c->gruns + (size_t)gdec2::MAX_RUNS * gdec2::RUN_WORDS,
-                               c->wgs_dec_gen, st, c->stream, true);
-        if (le != hipSuccess) {
-            set_err(err, "To decode launch failed: %s", hipGetErrorString(le));
-            ok = false;
+    bool took = false;  // the fast decoder took the frame
+    if (try_fast) {
+        if (!begin_call(c, &st, &slot, err)) return false;
+        // one buffer for both decoders, so that a fallback does not reallocate
+        bool ok = ensure_glws(c, std::max(nxg_wfast_scratch_bytes(len), nxg_dec_gen_scratch_bytes(len)),
+                              err);
+        if (ok) {
+            const ColsDesc d = desc_of(target, &wtarget);
+            const hipError_t le = nxg_launch_dec_wfast(df, len, d, reinterpret_cast<uint8_t*>(c->glws),
+                                                       st, c->stream);
+            if (le != hipSuccess) {
+                set_err(err, "fast To decode launch failed: %s", hipGetErrorString(le));
+                ok = false;
+            }
         }
+        if (!end_call(c, err) || !ok) return false;
+        HIPCHK(hipMemcpyAsync(c->hst + slot, st, sizeof(DevStatus), hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        took = !c->hst[slot].fast_fail;
     }
-    if (!end_call(c, err) || !ok) return false;
+    if (!took) {
+        if (!begin_call(c, &st, &slot, err)) return false;
+        bool ok = ensure_glws(c, nxg_dec_gen_scratch_bytes(len), err);
+        if (ok) {
+            const ColsDesc d = desc_of(target, &wtarget);
+            const hipError_t le =
+                nxg_launch_dec_gen(df, len, d, c->glws, c->gruns,
+                                   c->gruns + (size_t)gdec2::MAX_RUNS * gdec2::RUN_WORDS,
+                                   c->wgs_dec_gen, st, c->stream, true);
+            if (le != hipSuccess) {
+                set_err(err, "To decode launch failed: %s", hipGetErrorString(le));
+                ok = false;
+            }
+        }
+        if (!end_call(c, err) || !ok) return false;
+    }
     NxgStatus s;
-    if (!finish_decode(c, df, len, target, FAST_NONE, st, slot, &s, err)) return false;
-    s.path = NXG_PATH_WRITES;
+    if (!finish_decode(c, df, len, target, FAST_NONE, st, slot, &s, err, took)) return false;
+    s.path = took ? NXG_PATH_WRITES_FAST : NXG_PATH_WRITES;
     s.n_heartbeat = 0;
     out->layout = NXG_LAYOUT_MIXED;
     out->n_heartbeat = 0;

@@ -221,6 +221,13 @@ hipError_t nxg_launch_dec_fmx(const uint8_t* wire, uint64_t W, const ColsDesc& c
 hipError_t nxg_launch_dec_fmx_range(const uint8_t* wire, uint64_t W, uint64_t begin, uint64_t end,
                                     const ColsDesc& cols, uint8_t* scratch, const int* wgs,
                                     DevStatus* st, hipStream_t s, bool lean_count = false);
+// fast To decode (nxg_decode_writes_fast.hip): frames of Writes with flat values, Unsubscribes and
+// Subscribes of at most 256 bytes; sets fast_fail for anything else (and for columns too small).
+// `scratch`: nxg_wfast_scratch_bytes(W), no zeroing. Only frames nxg_wfast_takes(W) accepts.
+uint64_t nxg_wfast_scratch_bytes(uint64_t W);
+bool nxg_wfast_takes(uint64_t W);
+hipError_t nxg_launch_dec_wfast(const uint8_t* wire, uint64_t W, const ColsDesc& cols,
+                                uint8_t* scratch, DevStatus* st, hipStream_t s);
 // subscriber dispatch (nxg_dispatch.hip): `scratch` holds nxg_disp_scratch_bytes(n, n_chans)
 // bytes (no initialisation needed); `unmatched` one u64.
 uint64_t nxg_disp_scratch_bytes(uint64_t n, uint32_t n_chans);
