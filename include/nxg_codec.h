@@ -710,6 +710,144 @@ bool nxg_route_subscribes(NxgCtx* ctx, const NxgSubscribeTable* tab, const uint8
                           const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
                           const uint32_t* span_perm, NxgSubscribeRoute* out, NetidxError* err);
 
+/* ---- reply routing: replaces ConnectionCtx::process_batch (netidx/src/subscriber/
+ * connection.rs:409-541) and unsubscribe() (connection.rs:67-83) ---------------------------------
+ * The subscriber's side of a frame that holds a message other than an Update (decode_task,
+ * connection.rs:218-226, sends every such frame to process_batch; the publisher's Heartbeat makes
+ * one every idle second, and the reply to a Subscribe burst is one): the rows and control spans of
+ * one decoded From frame (nxg_decode_updates, device MIXED columns; control variants 0 NoSuchValue,
+ * 1 Denied, 2 Unsubscribed, 3 Subscribed, 5 Heartbeat, 6 WriteResult), in message order. Control
+ * span k precedes row ctl_row[k]; spans with equal ctl_row are in k order. An all-Update frame
+ * (n_ctl == 0) stays with nxg_dispatch_updates; this call has process_batch semantics even then
+ * (rows without a subscription are answered).
+ *
+ * State, built by the host for one connection (arrays in device memory, structs in host memory):
+ *   subs       the connection's subscriptions, exactly as nxg_dispatch_updates takes them, plus one
+ *              slot per pending request: the slot its subscription will occupy, with the request's
+ *              sub_id, its stream list (req.streams deduplicated by channel in order: what the
+ *              handle_connect_stream loop of connection.rs:521-528 leaves in sub.streams) and
+ *              slot_has_last 0 if one of those streams carries STOP_COLLECTING_LAST
+ *              (connection.rs:350-353), else 1. slot_of_id names live subscriptions only.
+ *   pending    `pending: HashMap<Path, SubscribeValRequest>` as a path table: the path's exact
+ *              bytes -> q, the request's index (the table's id is q)
+ *   pend_slot  [n_pending]: the slot of request q, < subs->n_slots
+ *   pend_alive [n_pending]: 0 if the request's `finished` receiver is known to be gone
+ *              (connection.rs:501-505); NULL: all alive
+ * The device decides plain paths only (nxg_path_is_plain), as nxg_route_subscribes does.
+ *
+ * "Subscribed at that point": slot_of_id[id], unless an earlier span of this call changed it: none
+ * after an Unsubscribed(id) that removed it, pend_slot[q] after a Subscribed with outcome
+ * NXG_REPLY_SUBSCRIBED. An Id >= n_ids has no subscription. Per message:
+ *   Update(id, v), row i, subscribed: one entry (slot_sub_id, i) per stream of the slot, in stream
+ *       order, appended to that stream's channel; last_row[slot] = 1 + i when the slot keeps `last`
+ *       (connection.rs:419-431)
+ *   Update(id, v), row i, not subscribed: To::Unsubscribe(id) is queued (connection.rs:432), once
+ *       per such row; counted in disp.n_unmatched
+ *   Heartbeat                     NXG_REPLY_NONE
+ *   WriteResult                   NXG_REPLY_WRITE_RESULT: reported only. pending_writes reads and
+ *       changes nothing else in the batch (connection.rs:435-445): matching (id, wid) is the host's
+ *   NoSuchValue / Denied(path)    NXG_REPLY_FAILED if the path is in `pending` and no earlier
+ *       variant-0/1/3 span of this call named it (pending.remove, connection.rs:447, 452):
+ *       span_q[k] = q, and the host sends the error the variant implies. Else NXG_REPLY_NONE.
+ *   Unsubscribed(id)              NXG_REPLY_UNSUBSCRIBED if subscribed at that point: one entry
+ *       (slot_sub_id, NXG_ENT_SPAN | k) per stream of the slot (unsubscribe(), connection.rs:74-80),
+ *       (id, slot) appended to unsub_id[] / unsub_slot[], and from there on the Id has no
+ *       subscription. Else NXG_REPLY_NONE.
+ *   Subscribed(path, id, m)       NXG_REPLY_ORPHAN on a pending miss (absent, or named earlier in
+ *       this call): To::Unsubscribe(id) (connection.rs:464-467). On a hit with the Id not
+ *       subscribed: NXG_REPLY_DROPPED if pend_alive[q] == 0: To::Unsubscribe(id), no subscription
+ *       (connection.rs:502-505); else NXG_REPLY_SUBSCRIBED: (k, q, id) appended to sub_span[] /
+ *       sub_q[] / sub_id[], and from there on the Id's slot is pend_slot[q] (connection.rs:491-517).
+ *       A hit with the Id subscribed at that point (an alias, connection.rs:468-490) or with
+ *       id >= n_ids is the host's message (stop 2).
+ * span_id[k] is the Id of a variant-2/3 span, else NXG_NO_ID; span_q[k] is q for FAILED, SUBSCRIBED
+ * and DROPPED, else NXG_NO_ID. Every To::Unsubscribe(id) goes out as varint(L) 01 varint(id),
+ * L = lw(1 + vl(id)), always one byte; the reply frame holds them in message order, rows and spans
+ * interleaved.
+ *
+ * Where a call stops (next_row, next_ctl, stopped):
+ *   0  the end: next_ctl == n_ctl and next_row == n_rows
+ *   1  span next_ctl is a Subscribed or Unsubscribed whose Id (< n_ids: an Id outside the table
+ *      has no state to change) an earlier Subscribed or Unsubscribed span of this call already
+ *      named, whatever that span's outcome. The call has processed the spans before it and the rows
+ *      before ctl_row[next_ctl] = next_row. The host applies the outputs (slot_of_id from sub_* and
+ *      unsub_*, nxg_path_table_remove of the paths with span_q[k] != NXG_NO_ID) and calls again
+ *      with (next_row, next_ctl). So inside one call each Id changes state at most once.
+ *   2  span next_ctl is the host's: a path that is not plain (variants 0, 1, 3), an alias, or a hit
+ *      with an Id outside the table. The host applies the outputs, handles that one message,
+ *      updates the tables and resumes at (next_row, next_ctl + 1). A span that is both (a path
+ *      that is not plain, an Id named before) stops with 2.
+ * The stop is the lowest such span, whatever the scheduling.
+ *
+ * Left to the host: stream_batch, the BEGIN_WITH_LAST initial values of new subscriptions
+ * (connection.rs:341-349, 521-528), which the reference runs after the whole batch (connection.rs:
+ * 535-536) through process_updates_batch: the host runs them after the last call, from sub_span[],
+ * through nxg_dispatch_updates or by hand; pending_writes; the durable_* and `subscribed`
+ * bookkeeping of unsubscribe() (connection.rs:84-117); setting `last` to Event::Unsubscribed from
+ * unsub_slot[], after applying last_row; send_updates. */
+#define NXG_ENT_SPAN (1ull << 63) /* ent_row: Event::Unsubscribed of span ent_row & ~NXG_ENT_SPAN */
+enum NxgReplyOutcome {
+    NXG_REPLY_NONE = 0,
+    NXG_REPLY_WRITE_RESULT = 1,
+    NXG_REPLY_FAILED = 2,
+    NXG_REPLY_UNSUBSCRIBED = 3,
+    NXG_REPLY_ORPHAN = 4,
+    NXG_REPLY_DROPPED = 5,
+    NXG_REPLY_SUBSCRIBED = 6
+};
+typedef struct NxgReplyTable {
+    const NxgSubTable* subs;
+    const NxgPathTable* pending;
+    uint64_t n_pending;
+    const uint32_t* pend_slot; /* [n_pending] */
+    const uint8_t* pend_alive; /* [n_pending], or NULL */
+} NxgReplyTable;
+/* Capacities and device arrays from the caller, counts written by the call. A-priori bounds for
+ * R rows and K spans: entries <= (R + K) * the longest stream list, reply bytes <= 12 * (R + K),
+ * sub <= K, unsub <= K. */
+typedef struct NxgReplyRoute {
+    uint64_t cap_spans;  /* outcome[] / span_q[] / span_id[] entries, >= cols->n_ctl */
+    uint8_t* outcome;    /* [cap_spans]: NxgReplyOutcome of span k, for the processed spans */
+    uint64_t* span_q;
+    uint64_t* span_id;
+    /* per channel c the entries [chan_off[c], chan_off[c+1]) in message order: ent_row is the
+     * Update's row, or NXG_ENT_SPAN | k for Event::Unsubscribed; last_row[n_slots]; n_unmatched =
+     * the rows answered with Unsubscribe */
+    NxgDispatch disp;
+    uint64_t cap_sub;    /* the SUBSCRIBED spans, in order: span, request, Id */
+    uint64_t* sub_span;
+    uint64_t* sub_q;
+    uint64_t* sub_id;
+    uint64_t cap_unsub;  /* the UNSUBSCRIBED spans, in order: Id and the slot it had */
+    uint64_t* unsub_id;
+    uint32_t* unsub_slot;
+    uint64_t cap_reply;  /* the reply frame's payload */
+    uint8_t* reply;
+    /* written by the call */
+    uint64_t n_entries, n_sub, n_unsub;
+    uint64_t n_replies;    /* messages in `reply` */
+    uint64_t reply_len;    /* bytes in `reply` */
+    uint64_t n_outcome[7]; /* processed spans per NxgReplyOutcome */
+    uint64_t next_row, next_ctl;
+    uint32_t stopped;      /* 0, 1 or 2, above */
+    uint32_t pad;
+} NxgReplyRoute;
+/* `frame` is the device frame the columns were decoded from. The decode validated every span
+ * (path UTF-8, varints, values); the call re-reads only varint(L) variant, then varint(|p|) path
+ * [varint(id)] or varint(id), the paths in aligned 8-byte words, and accepts a non-canonical L and
+ * trailing bytes inside the wrap as the decode accepted them. A call covers fewer than 2^32 rows
+ * and spans. One synchronisation; synchronous; scratch is the ctx's. Returns false on misuse,
+ * before any launch, with a message that names the field (host or F64-layout columns, a null
+ * array, ctl_begin > n_ctl, row_begin > n_rows, a pointer that is not device memory, async work
+ * pending on the ctx); on a HIP failure; when a path of the frame names a request q >= n_pending
+ * or with pend_slot[q] >= subs->n_slots (found on the device; the message names the lowest such
+ * span); or when a capacity is exceeded (NXG_CAPACITY in the message): the counts then hold the
+ * required values (n_entries, n_sub, n_unsub, reply_len) and the arrays hold what fitted, as
+ * nxg_route_writes does. */
+bool nxg_route_replies(NxgCtx* ctx, const NxgReplyTable* tab, const uint8_t* frame,
+                       const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
+                       NxgReplyRoute* out, NetidxError* err);
+
 /* ---- type-partitioned view of decoded mixed columns (optional output) --------
  * Replaces the per-value 28-way `match` on the tag (Value::decode, netidx-value/src/lib.rs:470-506)
  * for a consumer that handles values by type: the rows of `cols` grouped by their tag column, on

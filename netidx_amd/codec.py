@@ -142,6 +142,23 @@ class NxgSubscribeRoute(C.Structure):
                 ("stopped", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class NxgReplyTable(C.Structure):
+    _fields_ = [("subs", C.c_void_p), ("pending", C.c_void_p), ("n_pending", C.c_uint64),
+                ("pend_slot", C.c_void_p), ("pend_alive", C.c_void_p)]
+
+
+class NxgReplyRoute(C.Structure):
+    _fields_ = [("cap_spans", C.c_uint64), ("outcome", C.c_void_p), ("span_q", C.c_void_p),
+                ("span_id", C.c_void_p), ("disp", NxgDispatch),
+                ("cap_sub", C.c_uint64), ("sub_span", C.c_void_p), ("sub_q", C.c_void_p),
+                ("sub_id", C.c_void_p), ("cap_unsub", C.c_uint64), ("unsub_id", C.c_void_p),
+                ("unsub_slot", C.c_void_p), ("cap_reply", C.c_uint64), ("reply", C.c_void_p),
+                ("n_entries", C.c_uint64), ("n_sub", C.c_uint64), ("n_unsub", C.c_uint64),
+                ("n_replies", C.c_uint64), ("reply_len", C.c_uint64),
+                ("n_outcome", C.c_uint64 * 7), ("next_row", C.c_uint64),
+                ("next_ctl", C.c_uint64), ("stopped", C.c_uint32), ("pad", C.c_uint32)]
+
+
 TAG_BINS = 256
 
 
@@ -284,6 +301,9 @@ SIGNATURES = {
                                         C.POINTER(NxgColumns), C.c_uint64, C.c_uint64,
                                         C.c_void_p, C.POINTER(NxgSubscribeRoute),
                                         C.POINTER(NetidxError)]),
+    "nxg_route_replies": (C.c_bool, [C.c_void_p, C.POINTER(NxgReplyTable), C.c_void_p,
+                                     C.POINTER(NxgColumns), C.c_uint64, C.c_uint64,
+                                     C.POINTER(NxgReplyRoute), C.POINTER(NetidxError)]),
     "nxg_decode_range": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                     C.POINTER(NxgColumns), C.POINTER(NxgRange),
                                     C.POINTER(NetidxError)]),
@@ -1115,6 +1135,64 @@ class Codec:
         _check(ok, err)
         return r
 
+    def route_replies(self, table, frame, cols, row_begin=0, ctl_begin=0, cap_entries=None,
+                      cap_sub=None, cap_unsub=None, cap_reply=None):
+        """ConnectionCtx::process_batch (subscriber/connection.rs:409-541) for a decoded From frame
+        that holds control messages: `frame` is the device tensor decode_into read, `cols` the
+        MIXED columns it filled, `table` a ReplyTable. Processes rows and control spans from
+        (row_begin, ctl_begin) to the end or to a stop and returns a ReplyRoute (outcome, request
+        and Id per span, per-channel entries, last_row, the subscribed and unsubscribed lists, the
+        reply frame of To::Unsubscribe messages, next_row / next_ctl / stopped). Capacities default
+        to the a-priori bounds; one that is exceeded raises RouteCapacity carrying the required
+        counts."""
+        import torch
+        dev = cols.device
+        n_rows, n_ctl = int(cols.s.n_rows), int(cols.s.n_ctl)
+        rows, spans = max(n_rows - row_begin, 0), max(n_ctl - ctl_begin, 0)
+        cap_entries = (rows + spans) * table.max_fanout if cap_entries is None else cap_entries
+        cap_sub = spans if cap_sub is None else cap_sub
+        cap_unsub = spans if cap_unsub is None else cap_unsub
+        cap_reply = 12 * (rows + spans) if cap_reply is None else cap_reply
+        if not hasattr(frame, "data_ptr") or frame.device.type != "cuda":
+            raise CodecError("frame: the device tensor the columns were decoded from")
+
+        def buf(n, dt=torch.int64):
+            return torch.empty(max(int(n), 1), dtype=dt, device=dev)
+
+        r = ReplyRoute()
+        r.row_begin, r.ctl_begin = row_begin, ctl_begin
+        r.outcome = buf(n_ctl, torch.uint8)
+        r.span_q, r.span_id = buf(n_ctl), buf(n_ctl)
+        r.chan_off = torch.zeros(table.subs.n_chans + 1, dtype=torch.int64, device=dev)
+        r.ent_sub, r.ent_row = buf(cap_entries), buf(cap_entries)
+        r.last_row = buf(table.subs.slot_sub_id.numel())
+        r.sub_span, r.sub_q, r.sub_id = buf(cap_sub), buf(cap_sub), buf(cap_sub)
+        r.unsub_id, r.unsub_slot = buf(cap_unsub), buf(cap_unsub, torch.int32)
+        r.reply = buf(cap_reply, torch.uint8)
+        torch.cuda.synchronize(dev)  # (as Columns: the zero fill is done)
+        s = r.s
+        s.cap_spans = max(n_ctl, 1)
+        s.outcome, s.span_q, s.span_id = (r.outcome.data_ptr(), r.span_q.data_ptr(),
+                                          r.span_id.data_ptr())
+        s.disp = NxgDispatch(cap_entries, r.chan_off.data_ptr(), r.ent_sub.data_ptr(),
+                             r.ent_row.data_ptr(), r.last_row.data_ptr(), 0, 0)
+        s.cap_sub, s.sub_span, s.sub_q, s.sub_id = (cap_sub, r.sub_span.data_ptr(),
+                                                    r.sub_q.data_ptr(), r.sub_id.data_ptr())
+        s.cap_unsub, s.unsub_id, s.unsub_slot = (cap_unsub, r.unsub_id.data_ptr(),
+                                                 r.unsub_slot.data_ptr())
+        s.cap_reply, s.reply = cap_reply, r.reply.data_ptr()
+        tb = table.c_struct()
+        err = NetidxError()
+        ok = lib().nxg_route_replies(self.ctx, C.byref(tb), C.c_void_p(frame.data_ptr()),
+                                     C.byref(cols.s), row_begin, ctl_begin, C.byref(s),
+                                     C.byref(err))
+        if not ok and err.msg and b"NXG_CAPACITY" in err.msg:
+            msg = err.msg.decode()
+            lib().nxg_error_free(C.byref(err))
+            raise RouteCapacity(msg, r)
+        _check(ok, err)
+        return r
+
     def decode_range(self, dframe, frame_len, begin, end, cols):
         """Decode the messages that start in [begin, end) of a device frame (rows at cols[0:]);
         returns the NxgRange summary (entry / exit / n_rows / ok)."""
@@ -1644,6 +1722,83 @@ class SubscribeRoute:
                 "sub": list(zip(u(self.sub_id, n_sub).tolist(),
                                 self.sub_perm[:n_sub].cpu().numpy().view(np.uint32).tolist())),
                 "deferred": u(self.deferred, n_def).tolist(),
+                "reply": self.reply[:min(self.reply_len, self.reply.numel())].cpu().numpy()
+                .tobytes()}
+
+
+ENT_SPAN = 1 << 63  # NXG_ENT_SPAN: the entry is Event::Unsubscribed of span ent_row & ~ENT_SPAN
+(REPLY_NONE, REPLY_WRITE_RESULT, REPLY_FAILED, REPLY_UNSUBSCRIBED, REPLY_ORPHAN, REPLY_DROPPED,
+ REPLY_SUBSCRIBED) = range(7)
+
+
+class ReplyTable:
+    """A connection's state for Codec.route_replies (include/nxg_codec.h NxgReplyTable): `subs` a
+    SubTable that also holds one slot per pending request, `pending` a PathTable mapping each
+    pending path to its request's index q, pend_slot[q] the request's slot, pend_alive[q] 0 when
+    its `finished` receiver is gone (None: all alive)."""
+
+    def __init__(self, subs, pending, pend_slot, pend_alive=None, device="cuda"):
+        import torch
+        self.subs, self.pending = subs, pending
+        self.n_pending = len(pend_slot)
+        self.pend_slot = torch.as_tensor(
+            np.array(pend_slot, dtype=np.uint32).view(np.int32)).to(device)
+        self.pend_alive = None if pend_alive is None else torch.as_tensor(
+            np.array(pend_alive, dtype=np.uint8)).to(device)
+        off = subs.slot_stream_off.cpu().numpy().view(np.uint32).astype(np.int64)
+        self.max_fanout = int(np.diff(off).max()) if len(off) > 1 else 0
+
+    def c_struct(self):
+        self._subs = self.subs.c_struct()  # (kept alive through the call)
+        return NxgReplyTable(C.addressof(self._subs), self.pending.h, self.n_pending,
+                             self.pend_slot.data_ptr() if self.n_pending else None,
+                             None if self.pend_alive is None or not self.n_pending
+                             else self.pend_alive.data_ptr())
+
+
+class ReplyRoute:
+    """What Codec.route_replies returns (include/nxg_codec.h NxgReplyRoute): device tensors
+    outcome / span_q / span_id (per span of the columns), chan_off / ent_sub / ent_row / last_row
+    (as Dispatch), sub_span / sub_q / sub_id, unsub_id / unsub_slot and reply, with the counts in
+    `s`."""
+
+    def __init__(self):
+        self.s = NxgReplyRoute()
+        self.row_begin = self.ctl_begin = 0
+
+    def __getattr__(self, k):
+        s = self.__dict__.get("s")
+        if s is not None and k in ("n_entries", "n_sub", "n_unsub", "n_replies", "reply_len",
+                                   "next_row", "next_ctl", "stopped"):
+            return int(getattr(s, k))
+        raise AttributeError(k)
+
+    @property
+    def n_outcome(self):
+        return [int(x) for x in self.s.n_outcome]
+
+    @property
+    def n_unmatched(self):
+        return int(self.s.disp.n_unmatched)
+
+    def batches(self):
+        """{chan: [(sub_id, row | ENT_SPAN | span), ...]} on the host (non-empty channels only)."""
+        return Dispatch(self.chan_off, self.ent_sub, self.ent_row, self.last_row,
+                        min(self.n_entries, self.ent_sub.numel()), self.n_unmatched).batches()
+
+    def numpy(self):
+        """Host copies, trimmed to what the call wrote (and to the capacities)."""
+        u = lambda t, n: t[:min(n, t.numel())].cpu().numpy().view(np.uint64).tolist()
+        k0, k1 = self.ctl_begin, self.next_ctl
+        return {"outcome": self.outcome[k0:k1].cpu().numpy().tolist(),
+                "span_q": self.span_q[k0:k1].cpu().numpy().view(np.uint64).tolist(),
+                "span_id": self.span_id[k0:k1].cpu().numpy().view(np.uint64).tolist(),
+                "sub": list(zip(u(self.sub_span, self.n_sub), u(self.sub_q, self.n_sub),
+                                u(self.sub_id, self.n_sub))),
+                "unsub": list(zip(u(self.unsub_id, self.n_unsub),
+                                  self.unsub_slot[:min(self.n_unsub, self.unsub_slot.numel())]
+                                  .cpu().numpy().view(np.uint32).tolist())),
+                "last_row": self.last_row.cpu().numpy().view(np.uint64).tolist(),
                 "reply": self.reply[:min(self.reply_len, self.reply.numel())].cpu().numpy()
                 .tobytes()}
 

@@ -136,6 +136,12 @@ struct NxgCtx {
     uint64_t* rw_first = nullptr;
     size_t rw_first_cap = 0;
     uint32_t rw_epoch = 0;
+    // reply routing (nxg_route_replies.hip): the first span per Id and per pending request, tagged
+    // likewise with one epoch for both
+    uint64_t* rr_first_id = nullptr;
+    uint64_t* rr_first_q = nullptr;
+    size_t rr_first_id_cap = 0, rr_first_q_cap = 0;
+    uint32_t rr_epoch = 0;
     // in-flight async operations (completed in order by nxg_ctx_sync)
     struct Pending {
         int kind;  // 1 decode, 2 encode
@@ -1051,6 +1057,8 @@ void nxg_ctx_destroy(NxgCtx* c) {
     if (c->dwflags) (void)hipFree(c->dwflags);
     if (c->dwid) (void)hipFree(c->dwid);
     if (c->rw_first) (void)hipFree(c->rw_first);
+    if (c->rr_first_id) (void)hipFree(c->rr_first_id);
+    if (c->rr_first_q) (void)hipFree(c->rr_first_q);
     if (c->dst) (void)hipFree(c->dst);
     if (c->hst) (void)hipHostFree(c->hst);
     if (c->own) (void)hipStreamDestroy(c->own);
@@ -3519,6 +3527,219 @@ bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t
                 (unsigned long long)out->n_sub, (unsigned long long)out->n_deferred,
                 (unsigned long long)out->reply_len, (unsigned long long)out->cap_sub,
                 (unsigned long long)out->cap_deferred, (unsigned long long)out->cap_reply);
+        return false;
+    }
+    return true;
+}
+
+// ---- reply routing (subscriber/connection.rs:67-83, 409-541) ------------------------------------
+namespace {
+// an epoch-tagged table of the ctx, grown (and cleared) on demand, never cleared per call
+bool rr_table(NxgCtx* c, uint64_t** tab, size_t* cap, uint64_t want, NetidxError* err) {
+    if (want <= *cap) return true;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (*tab) HIPCHK(hipFree(*tab));
+    *tab = nullptr;
+    *cap = 0;
+    const size_t n = std::max<size_t>(want, 4096);
+    HIPCHK(hipMalloc(tab, n * 8));
+    HIPCHK(hipMemsetAsync(*tab, 0, n * 8, c->stream));
+    *cap = n;
+    return true;
+}
+}  // namespace
+
+// Replaces process_batch: nxg_route_replies.hip's passes, the dispatch of nxg_dispatch.hip over the
+// call's items for the fan-out, one copy of the head, one synchronisation.
+bool nxg_route_replies(NxgCtx* c, const NxgReplyTable* tab, const uint8_t* frame,
+                       const NxgColumns* cols, uint64_t row_begin, uint64_t ctl_begin,
+                       NxgReplyRoute* out, NetidxError* err) {
+    // (the argument checks come before any use of the context)
+    if (!c || !cols || !out) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!tab || !tab->subs || !tab->pending) {
+        set_err(err, "tab: the table, tab->subs or tab->pending is null");
+        return false;
+    }
+    if (cols->mem != NXG_MEM_DEVICE) {
+        set_err(err, "cols->mem: reply routing takes device columns");
+        return false;
+    }
+    if (cols->layout != NXG_LAYOUT_MIXED || !mixed_capable(cols)) {
+        set_err(err, "cols->layout: frames with control messages are decoded into MIXED-layout "
+                     "columns");
+        return false;
+    }
+    const uint64_t n_rows = cols->n_rows, n_ctl = cols->n_ctl;
+    if (row_begin > n_rows) {
+        set_err(err, "row_begin %llu is past the batch's %llu rows", (unsigned long long)row_begin,
+                (unsigned long long)n_rows);
+        return false;
+    }
+    if (ctl_begin > n_ctl) {
+        set_err(err, "ctl_begin %llu is past the batch's %llu control spans",
+                (unsigned long long)ctl_begin, (unsigned long long)n_ctl);
+        return false;
+    }
+    const uint64_t rows = n_rows - row_begin, spans = n_ctl - ctl_begin;
+    if (rows + spans >= 0xffffffffull) {
+        set_err(err, "row_begin / ctl_begin: a call covers fewer than 2^32 rows and spans");
+        return false;
+    }
+    const NxgSubTable* st = tab->subs;
+    if (out->cap_spans < n_ctl) {
+        set_err(err, "out->cap_spans: outcome[] / span_q[] / span_id[] hold %llu spans, the batch "
+                     "%llu", (unsigned long long)out->cap_spans, (unsigned long long)n_ctl);
+        return false;
+    }
+    if (tab->pending->device != c->device) {
+        set_err(err, "tab->pending belongs to device %d, the ctx to %d", tab->pending->device,
+                c->device);
+        return false;
+    }
+    // every pointer a kernel gets is device memory (a host pointer would fault there)
+    struct {
+        const void* p;
+        bool need;
+        const char* name;
+    } const ptrs[] = {
+        {frame, spans != 0, "frame"},
+        {cols->id, rows != 0, "cols->id"},
+        {cols->ctl_row, n_ctl != 0, "cols->ctl_row"},
+        {cols->ctl_off, spans != 0, "cols->ctl_off"},
+        {cols->ctl_len, spans != 0, "cols->ctl_len"},
+        {cols->ctl_variant, spans != 0, "cols->ctl_variant"},
+        {st->slot_of_id, st->n_ids != 0, "tab->subs->slot_of_id"},
+        {st->slot_sub_id, st->n_slots != 0, "tab->subs->slot_sub_id"},
+        {st->slot_stream_off, st->n_slots != 0, "tab->subs->slot_stream_off"},
+        {st->slot_has_last, st->n_slots != 0, "tab->subs->slot_has_last"},
+        {st->stream_chan, false, "tab->subs->stream_chan"},
+        {tab->pend_slot, tab->n_pending != 0, "tab->pend_slot"},
+        {tab->pend_alive, false, "tab->pend_alive"},
+        {out->outcome, n_ctl != 0, "out->outcome"},
+        {out->span_q, n_ctl != 0, "out->span_q"},
+        {out->span_id, n_ctl != 0, "out->span_id"},
+        {out->disp.chan_off, true, "out->disp.chan_off"},
+        {out->disp.ent_sub, out->disp.cap_entries != 0, "out->disp.ent_sub"},
+        {out->disp.ent_row, out->disp.cap_entries != 0, "out->disp.ent_row"},
+        {out->disp.last_row, st->n_slots != 0, "out->disp.last_row"},
+        {out->sub_span, out->cap_sub != 0, "out->sub_span"},
+        {out->sub_q, out->cap_sub != 0, "out->sub_q"},
+        {out->sub_id, out->cap_sub != 0, "out->sub_id"},
+        {out->unsub_id, out->cap_unsub != 0, "out->unsub_id"},
+        {out->unsub_slot, out->cap_unsub != 0, "out->unsub_slot"},
+        {out->reply, out->cap_reply != 0, "out->reply"},
+    };
+    for (const auto& q : ptrs) {
+        if ((q.p || q.need) && !is_device_ptr(q.p)) {
+            set_err(err, "%s: %s", q.name, q.p ? "not device memory" : "null");
+            return false;
+        }
+    }
+    if (st->n_slots && st->n_chans && !st->stream_chan) {
+        // (a table whose every stream list is empty may leave it null: no entry is ever read)
+        uint32_t last = 0;
+        HIPCHK(hipSetDevice(c->device));
+        HIPCHK(hipMemcpy(&last, st->slot_stream_off + st->n_slots, 4, hipMemcpyDeviceToHost));
+        if (last) {
+            set_err(err, "tab->subs->stream_chan: null");
+            return false;
+        }
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (!rr_table(c, &c->rr_first_id, &c->rr_first_id_cap, st->n_ids, err) ||
+        !rr_table(c, &c->rr_first_q, &c->rr_first_q_cap, tab->n_pending, err))
+        return false;
+    if (++c->rr_epoch >= (1u << 24)) {  // wrap: stale words could alias epoch 1 again
+        c->rr_epoch = 1;
+        if (c->rr_first_id)
+            HIPCHK(hipMemsetAsync(c->rr_first_id, 0, c->rr_first_id_cap * 8, c->stream));
+        if (c->rr_first_q)
+            HIPCHK(hipMemsetAsync(c->rr_first_q, 0, c->rr_first_q_cap * 8, c->stream));
+    }
+    const size_t rr = (nxg_rr_scratch_bytes(rows, spans) + 255) & ~size_t(255);
+    const size_t need = rr + 64 + nxg_disp_scratch_bytes(rows + spans, st->n_chans);
+    if (need > c->dscratch_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
+        c->dscratch = nullptr;
+        const size_t sz = std::max(need, c->dscratch_cap * 2);
+        c->dscratch_cap = 0;
+        HIPCHK(hipMalloc(&c->dscratch, sz));
+        c->dscratch_cap = sz;
+    }
+    NxgRrArgs a{};
+    a.subs = *st;
+    a.pending = tab->pending->v;
+    a.n_pending = tab->n_pending;
+    a.pend_slot = tab->pend_slot;
+    a.pend_alive = tab->pend_alive;
+    a.frame = frame;
+    a.id = cols->id;
+    a.ctl_row = cols->ctl_row;
+    a.ctl_off = cols->ctl_off;
+    a.ctl_len = cols->ctl_len;
+    a.ctl_variant = cols->ctl_variant;
+    a.n_rows = n_rows;
+    a.n_ctl = n_ctl;
+    a.row_begin = row_begin;
+    a.ctl_begin = ctl_begin;
+    a.first_id = c->rr_first_id;
+    a.first_q = c->rr_first_q;
+    a.epoch = c->rr_epoch;
+    a.outcome = out->outcome;
+    a.span_q = out->span_q;
+    a.span_id = out->span_id;
+    a.sub_span = out->sub_span;
+    a.sub_q = out->sub_q;
+    a.sub_id = out->sub_id;
+    a.cap_sub = out->cap_sub;
+    a.unsub_id = out->unsub_id;
+    a.unsub_slot = out->unsub_slot;
+    a.cap_unsub = out->cap_unsub;
+    a.reply = out->reply;
+    a.cap_reply = out->cap_reply;
+    a.last_row = out->disp.last_row;
+    HIPCHK(nxg_launch_route_replies(a, c->dscratch, c->dscratch + rr, out->disp.chan_off,
+                                    out->disp.ent_sub, out->disp.ent_row, out->disp.cap_entries,
+                                    c->ncu, c->stream));
+    NxgRrHead h;
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out->n_entries = out->disp.n_entries = h.n_entries;
+    out->disp.n_unmatched = h.n_unmatched;
+    out->n_sub = h.n_sub;
+    out->n_unsub = h.n_unsub;
+    out->n_replies = h.n_span_replies + h.n_unmatched;
+    out->reply_len = h.span_bytes + h.row_bytes;
+    for (int o = 0; o < 7; o++) out->n_outcome[o] = h.n_outcome[o];
+    out->next_row = h.next_row;
+    out->next_ctl = h.next_ctl;
+    out->stopped = h.stopped;
+    out->pad = 0;
+    if (h.bad_inv) {
+        const uint64_t bad_k = ~(h.bad_inv >> 8 | 0xffull << 56);
+        set_err(err, (h.bad_inv & 0xff) == 1
+                         ? "tab->pending: the path of span %llu maps to a request >= tab->n_pending"
+                         : "tab->pend_slot: the request of span %llu's path has a slot >= "
+                           "tab->subs->n_slots",
+                (unsigned long long)bad_k);
+        return false;
+    }
+    if (h.n_entries > out->disp.cap_entries || out->n_sub > out->cap_sub ||
+        out->n_unsub > out->cap_unsub || out->reply_len > out->cap_reply) {
+        set_err(err, "reply routing needs %llu entries, %llu subscribed spans, %llu unsubscribed ids, "
+                     "%llu reply bytes; capacities are %llu, %llu, %llu, %llu (NXG_CAPACITY)",
+                (unsigned long long)h.n_entries, (unsigned long long)out->n_sub,
+                (unsigned long long)out->n_unsub, (unsigned long long)out->reply_len,
+                (unsigned long long)out->disp.cap_entries, (unsigned long long)out->cap_sub,
+                (unsigned long long)out->cap_unsub, (unsigned long long)out->cap_reply);
         return false;
     }
     return true;

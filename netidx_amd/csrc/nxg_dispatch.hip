@@ -50,9 +50,12 @@ struct Row {
 
 // Per-row routing (publisher commit, nxg_publish.hip): mode 0 = through the Id's slot, 1 = not
 // pushed (an unchanged UpdateChanged), 2 = to client to_client[i] only. `mode` null: all 0.
+// Per-item slots (reply routing, nxg_route_replies.hip): `slot` set: row i goes through slot
+// slot[i] (NONE: nowhere), whatever its Id; last_row is the caller's.
 struct Route {
     const uint8_t* mode;
     const uint32_t* to_client;
+    const uint32_t* slot;
 };
 
 NXG_DEV Row row_of(const NxgSubTable& tb, const Route& rt, const uint64_t* __restrict__ id,
@@ -68,9 +71,14 @@ NXG_DEV Row row_of(const NxgSubTable& tb, const Route& rt, const uint64_t* __res
             return r;
         }
         if (m == 1) return r;
-        const uint64_t x = id[i];
-        const uint32_t s = x < tb.n_ids ? tb.slot_of_id[x] : NONE;
-        unmatched = s == NONE;
+        uint32_t s;
+        if (rt.slot) {
+            s = rt.slot[i];
+        } else {
+            const uint64_t x = id[i];
+            s = x < tb.n_ids ? tb.slot_of_id[x] : NONE;
+            unmatched = s == NONE;
+        }
         if (s != NONE) {
             r.slot = s;
             r.k0 = tb.slot_stream_off[s];
@@ -223,7 +231,8 @@ __global__ __launch_bounds__(TPB, NXG_DISP_COCC) void nxg_disp_count_kernel(
                 const uint32_t ns = r.k1 - r.k0;
                 cache_put(rc, i, r.slot, ns, ns >= 1u ? r.c[0] : NONE, ns >= 2u ? r.c[1] : NONE);
             }
-            if (!(NXG_DISP_SKIP & 1) && r.slot != NONE && (!tb.slot_has_last || tb.slot_has_last[r.slot])) {
+            if (!(NXG_DISP_SKIP & 1) && r.slot != NONE && !rt.slot &&
+                (!tb.slot_has_last || tb.slot_has_last[r.slot])) {
                 if (plain_last) last_row[r.slot] = i + 1;
                 else if (NXG_DISP_A32 && n < 0xffffffffull)  // the low word (high words are 0)
                     atomicMax(reinterpret_cast<unsigned*>(&last_row[r.slot]), (unsigned)(i + 1));
@@ -512,8 +521,9 @@ hipError_t nxg_launch_dispatch(const NxgSubTable& tb, const uint64_t* id, uint64
                                uint8_t* scratch, uint64_t* chan_off, uint64_t* ent_sub,
                                uint64_t* ent_row, uint64_t cap, uint64_t* last_row,
                                uint64_t* unmatched, int ncu, hipStream_t s,
-                               const uint8_t* row_mode, const uint32_t* to_client) {
-    const Route rt{row_mode, to_client};
+                               const uint8_t* row_mode, const uint32_t* to_client,
+                               const uint32_t* item_slot) {
+    const Route rt{row_mode, to_client, item_slot};
     const uint64_t seg = nxg_disp_seg_rows(n, tb.n_chans);
     const uint64_t n_seg = (n + seg - 1) / seg;
     const uint64_t M = n_seg * (uint64_t)tb.n_chans;
@@ -531,7 +541,9 @@ hipError_t nxg_launch_dispatch(const NxgSubTable& tb, const uint64_t* id, uint64
     }
     hipError_t e;
     if ((e = hipMemsetAsync(unmatched, 0, 8, s)) != hipSuccess) return e;
-    if (tb.n_slots && (e = hipMemsetAsync(last_row, 0, tb.n_slots * 8, s)) != hipSuccess) return e;
+    if (tb.n_slots && !item_slot &&
+        (e = hipMemsetAsync(last_row, 0, tb.n_slots * 8, s)) != hipSuccess)
+        return e;
     const bool fuse = NXG_DISP_FUSE && M != 0 && tb.n_chans <= LCH;
     if (!fuse && (e = hipMemsetAsync(chan_off, 0, ((uint64_t)tb.n_chans + 1) * 8, s)) != hipSuccess)
         return e;
@@ -546,7 +558,7 @@ hipError_t nxg_launch_dispatch(const NxgSubTable& tb, const uint64_t* id, uint64
     const uint32_t g = (uint32_t)(want < gcap ? want : gcap);
     const bool in_lds = tb.n_chans <= LCH;
     // (no channels: no scatter to finish last_row, the count pass takes the atomics)
-    const bool plain_last = NXG_DISP_LASTP && M != 0;
+    const bool plain_last = NXG_DISP_LASTP && M != 0 && !item_slot;
     const size_t lds_count = in_lds ? (size_t)WAVES * tb.n_chans * 4 : 0;
     const size_t lds_scatter = in_lds ? (size_t)WAVES * tb.n_chans * 16 : 0;
     hipLaunchKernelGGL(nxg_disp_count_kernel, dim3(g), dim3(TPB), lds_count, s, tb, rt, id, n, seg,

@@ -229,14 +229,17 @@ bool nxg_wfast_takes(uint64_t W);
 hipError_t nxg_launch_dec_wfast(const uint8_t* wire, uint64_t W, const ColsDesc& cols,
                                 uint8_t* scratch, DevStatus* st, hipStream_t s);
 // subscriber dispatch (nxg_dispatch.hip): `scratch` holds nxg_disp_scratch_bytes(n, n_chans)
-// bytes (no initialisation needed); `unmatched` one u64.
+// bytes (no initialisation needed); `unmatched` one u64. item_slot (reply routing,
+// nxg_route_replies.hip): row i is an item whose slot is item_slot[i] (NXG_NO_SLOT: no entries);
+// no Id is looked up, nothing counts as unmatched and last_row is neither cleared nor written.
 uint64_t nxg_disp_scratch_bytes(uint64_t n, uint32_t n_chans);
 hipError_t nxg_launch_dispatch(const NxgSubTable& tb, const uint64_t* id, uint64_t n,
                                uint8_t* scratch, uint64_t* chan_off, uint64_t* ent_sub,
                                uint64_t* ent_row, uint64_t cap, uint64_t* last_row,
                                uint64_t* unmatched, int ncu, hipStream_t s,
                                const uint8_t* row_mode = nullptr,
-                               const uint32_t* to_client = nullptr);
+                               const uint32_t* to_client = nullptr,
+                               const uint32_t* item_slot = nullptr);
 // publisher commit (nxg_publish.hip): stage 1 counts slots and sets flags (dup, changed,
 // unsupported: three u32 at nxg_pub_flags(scratch)); stage 2 routes the UpdateChanged rows
 // (mode array for nxg_launch_dispatch, or null when the kinds route as they are).
@@ -537,3 +540,76 @@ struct NxgRsArgs {
 uint64_t nxg_rs_scratch_bytes(uint64_t spans);
 // a.head is at `scratch` afterwards; `scratch` needs no initialising
 hipError_t nxg_launch_route_subscribes(NxgRsArgs a, uint8_t* scratch, hipStream_t s);
+
+// reply routing (nxg_route_replies.hip): the call's head (device, zeroed per call, copied back
+// whole after the last launch) and the arguments every kernel of the call takes by value
+struct NxgRrHead {
+    uint64_t stop_inv;  // ~k of the first span k >= ctl_begin the call stops in front of
+                        // (atomicMax; 0: none)
+    uint64_t bad_inv;   // ~k << 8 | cause, of the first span k whose path names a request the
+                        // tables do not hold: 1 q >= n_pending, 2 pend_slot[q] >= n_slots
+    uint64_t span_bytes, row_bytes;  // reply bytes of the spans / of the rows
+    uint64_t n_span_replies, n_unmatched;
+    uint64_t n_sub, n_unsub;
+    uint64_t n_outcome[7];
+    uint64_t n_entries, next_row, next_ctl;
+    uint32_t stopped, pad1;
+    uint64_t pad[5];
+};
+static_assert(sizeof(NxgRrHead) == 192, "NxgRrHead layout");
+struct NxgRrArgs {
+    NxgSubTable subs;
+    NxgPtView pending;
+    uint64_t n_pending;
+    const uint32_t* pend_slot;
+    const uint8_t* pend_alive;
+    const uint8_t* frame;
+    const uint64_t* id;  // the decoded columns
+    const uint64_t* ctl_row;
+    const uint64_t* ctl_off;
+    const uint32_t* ctl_len;
+    const uint8_t* ctl_variant;
+    uint64_t n_rows, n_ctl, row_begin, ctl_begin;
+    // ctx-owned, never cleared: epoch << 40 | ~j of the first span ctl_begin + j of this call that
+    // names the Id (an Unsubscribed or Subscribed span) / the pending request's path
+    uint64_t* first_id;  // [>= n_ids]
+    uint64_t* first_q;   // [>= n_pending]
+    uint32_t epoch;
+    // outputs
+    uint8_t* outcome;
+    uint64_t* span_q;
+    uint64_t* span_id;
+    uint64_t* sub_span;
+    uint64_t* sub_q;
+    uint64_t* sub_id;
+    uint64_t cap_sub;
+    uint64_t* unsub_id;
+    uint32_t* unsub_slot;
+    uint64_t cap_unsub;
+    uint8_t* reply;
+    uint64_t cap_reply;
+    uint64_t* last_row;
+    // scratch, placed by the launcher
+    NxgRrHead* head;
+    uint64_t* sid;    // per span: its Id (variants 2, 3), or NXG_NO_ID
+    uint64_t* sq;     // per span: the request its path names (variants 0, 1, 3), or NXG_NO_ID
+    uint64_t* sloc;   // per span: bytes | replies | SUBSCRIBED | UNSUBSCRIBED before it in its block
+    uint64_t* zblk;   // per span block: reply bytes
+    uint64_t* nblk;   // per span block: replies
+    uint64_t* sblk;   // per span block: SUBSCRIBED spans
+    uint64_t* ublk;   // per span block: UNSUBSCRIBED spans
+    uint64_t* oblk;   // per span block, four arrays: outcomes 0 | 1 << 32, 2 | 3, 4 | 5, 6
+    uint64_t* rzblk;  // per row block: reply bytes
+    uint64_t* rnblk;  // per row block: replies
+    uint64_t* item_val;   // per item: the row, or NXG_ENT_SPAN | k
+    uint32_t* item_slot;  // per item: its slot at that point, or NXG_NO_SLOT
+    uint32_t* rloc;   // per row: reply bytes before it within its block, bit 31: it replies
+    uint8_t* skind;   // per span: the stop it would be (0: none; 1, 2; 3: 2, path not plain)
+};
+// `scratch` holds nxg_rr_scratch_bytes(rows from row_begin, spans from ctl_begin) bytes,
+// `disp_scratch` 64 + nxg_disp_scratch_bytes(those rows + spans, n_chans); neither needs
+// initialising. a.head is at `scratch` afterwards.
+uint64_t nxg_rr_scratch_bytes(uint64_t rows, uint64_t spans);
+hipError_t nxg_launch_route_replies(NxgRrArgs a, uint8_t* scratch, uint8_t* disp_scratch,
+                                    uint64_t* chan_off, uint64_t* ent_sub, uint64_t* ent_row,
+                                    uint64_t cap_entries, int ncu, hipStream_t s);
