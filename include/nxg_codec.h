@@ -920,6 +920,48 @@ bool nxg_publish_commit(NxgCtx* ctx, const NxgPubTable* tab, const NxgColumns* b
  * ent_row = the pair's index in the queue; last_row unused (may be NULL). Synchronous. */
 bool nxg_publish_unsubscribes(NxgCtx* ctx, const uint64_t* id, const uint32_t* client,
                               uint64_t n, uint32_t n_clients, NxgDispatch* out, NetidxError* err);
+/* The commit's per-client batches, encoded: replaces the gather of every column by each client's
+ * ent_row segment and one nxg_encode_updates call per client (handle_updates -> queue_send,
+ * publisher/server.rs:604-629). `batch`, `heap` and `d` are the arguments and the result of
+ * nxg_publish_commit, all device memory; batch may have either layout, must have n_ctl == 0, and
+ * its children arrays are used as they are. Entry e < d->n_entries becomes the message
+ *   varint(L) 04 varint(batch->id[r]) Value(row r),   r = d->ent_row[e],
+ * byte for byte what nxg_encode_updates writes for row r; d->ent_sub is not read. The entries are
+ * sorted by client, so the payloads lie back to back in client order: client c's is
+ * out[client_off[c], client_off[c+1]), one frame payload that the host sends behind its own
+ * nxg_frame_header. Entries may name rows in any order and any row any number of times.
+ * d->chan_off[0 .. n_clients] must not decrease and must end at d->n_entries. Any other chan_off
+ * fails the call: client_off is preset to all-ones, the tiles store the offsets of the clients
+ * they find, and the host requires what it reads back not to decrease and to end at the encoded
+ * total (a skipped client stays all-ones; offsets decrease exactly where chan_off does, since no
+ * message is empty). Entries before chan_off[0] are encoded in front of client 0's payload. One launch of a tile encoder
+ * that reads its rows through ent_row; no per-entry offsets are written.
+ * Synchronous; a pending async call on the ctx is refused. out->out NULL sizes only: client_off
+ * and n_bytes are filled and nothing else is written. false with err
+ *   on misuse (NULLs, host memory, n_ctl != 0);
+ *   when ent_row[e] >= batch->n_rows for an entry (checked on the device; the message names the
+ *     first such entry). Only rows that an entry names are looked at: an invalid value in a row
+ *     that no entry names does not fail the call;
+ *   on the content errors nxg_encode_updates reports for a row that an entry names (PackError
+ *     kind, TooBig);
+ *   when n_bytes > cap_bytes (n_bytes then holds what is needed);
+ *   when a client's payload exceeds MAX_BATCH = 0x3FFFFFFF bytes (the message names the first such
+ *     client and its length: encode that client's rows with nxg_encode_frames). With
+ *     cap_bytes > MAX_BATCH the call sizes first, so that such a call writes nothing; a size-only
+ *     call succeeds and reports the lengths.
+ * A failed call may leave any bytes inside [out, out + cap_bytes) and any values in client_off;
+ * whatever the outcome, no byte outside [out, out + cap_bytes) and no element outside
+ * client_off[0 .. n_clients] is written. d->n_entries == 0 gives all-zero client_off. */
+typedef struct NxgClientFrames {
+    uint64_t cap_bytes;   /* capacity of out */
+    uint8_t* out;         /* device; NULL: size only */
+    uint64_t* client_off; /* device, [n_clients + 1]: client c's payload is
+                             out[client_off[c], client_off[c+1]) */
+    uint64_t n_bytes;     /* written by the call: client_off[n_clients] */
+} NxgClientFrames;
+bool nxg_encode_clients(NxgCtx* ctx, const NxgColumns* batch, const uint8_t* heap,
+                        const NxgDispatch* d, uint32_t n_clients, NxgClientFrames* out,
+                        NetidxError* err);
 
 /* ---- archive batches: replaces <GPooled<Vec<BatchItem>> as Pack>::decode ------------------
  * (netidx-archive/src/logfile/reader.rs:449/475 over logfile/mod.rs:150-205 BatchItem and

@@ -107,6 +107,11 @@ class NxgDispatch(C.Structure):
                 ("n_unmatched", C.c_uint64)]
 
 
+class NxgClientFrames(C.Structure):
+    _fields_ = [("cap_bytes", C.c_uint64), ("out", C.c_void_p), ("client_off", C.c_void_p),
+                ("n_bytes", C.c_uint64)]
+
+
 class NxgWriteTable(C.Structure):
     _fields_ = [("n_ids", C.c_uint64), ("perm_of_id", C.c_void_p), ("slot_of_id", C.c_void_p),
                 ("n_slots", C.c_uint64), ("slot_chan_off", C.c_void_p), ("chan", C.c_void_p),
@@ -334,6 +339,9 @@ SIGNATURES = {
                                       C.POINTER(NetidxError)]),
     "nxg_publish_unsubscribes": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.c_uint32, C.c_void_p, C.POINTER(NetidxError)]),
+    "nxg_encode_clients": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
+                                      C.POINTER(NxgDispatch), C.c_uint32,
+                                      C.POINTER(NxgClientFrames), C.POINTER(NetidxError)]),
     "nxg_zstd_dict_new": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint64,
                                        C.POINTER(NetidxError)]),
     "nxg_zstd_dict_free": (None, [C.c_void_p]),
@@ -952,6 +960,49 @@ class Codec:
                                               C.c_void_p(clients.data_ptr()), n, n_clients,
                                               C.byref(out), C.byref(err)), err)
         return Dispatch(chan_off, ent_id, ent_row, chan_off[:0], out.n_entries, 0)
+
+    def encode_clients_into(self, batch, dispatch, heap, out_ptr, cap, client_off=None):
+        """nxg_encode_clients into device memory at `out_ptr` (0 / None: size only). `dispatch`:
+        a Dispatch (publish_commit's, or any chan_off / ent_row device tensors with n_entries).
+        Returns (n_bytes, client_off); a CodecError raised here carries n_bytes (what a buffer
+        too small would have needed) and client_off."""
+        import torch
+        n_clients = dispatch.chan_off.numel() - 1
+        if client_off is None:
+            client_off = torch.empty(n_clients + 1, dtype=torch.int64, device=batch.id.device)
+        d = NxgDispatch(dispatch.ent_row.numel(), dispatch.chan_off.data_ptr(),
+                        dispatch.ent_sub.data_ptr() if dispatch.ent_sub is not None else None,
+                        dispatch.ent_row.data_ptr(), None, int(dispatch.n_entries), 0)
+        o = NxgClientFrames(cap, out_ptr or None, client_off.data_ptr(), 0)
+        err = NetidxError()
+        try:
+            _check(lib().nxg_encode_clients(self.ctx, C.byref(batch.s), _heap_ptr(heap),
+                                            C.byref(d), n_clients, C.byref(o), C.byref(err)), err)
+        except CodecError as e:
+            e.n_bytes, e.client_off = int(o.n_bytes), client_off
+            raise
+        return int(o.n_bytes), client_off
+
+    def encoded_clients_len(self, batch, dispatch, heap=None):
+        """The size-only form of encode_clients: (n_bytes, client_off), nothing encoded."""
+        return self.encode_clients_into(batch, dispatch, heap, None, 0)
+
+    def encode_clients(self, batch, dispatch, heap=None, out=None):
+        """The commit's per-client batches in one call (handle_updates -> queue_send per client):
+        `batch` and `heap` as given to publish_commit, `dispatch` its result. Returns (bytes,
+        client_off): client c's frame payload is bytes[client_off[c]:client_off[c+1]] (uint8 /
+        int64 tensors on the batch's device). `out`: a uint8 device tensor to encode into (all of
+        it is the capacity); without one the call sizes first and allocates."""
+        import torch
+        off = None
+        if out is None:
+            n, off = self.encoded_clients_len(batch, dispatch, heap)
+            out = torch.empty(max(n, 16), dtype=torch.uint8, device=batch.id.device)
+            cap = n
+        else:
+            cap = out.numel()
+        n, off = self.encode_clients_into(batch, dispatch, heap, out.data_ptr(), cap, off)
+        return out[:n], off
 
     def encoded_len(self, cols, heap=None):
         n, err = C.c_uint64(0), NetidxError()

@@ -2681,6 +2681,135 @@ bool nxg_publish_unsubscribes(NxgCtx* c, const uint64_t* id, const uint32_t* cli
     return true;
 }
 
+// ---- the commit's per-client batches, encoded (handle_updates -> queue_send per client) -------
+// One gathered encode of the entry list (nxg_encode_clients.hip). pass(dout, cap) runs the tile
+// kernel and reads the status and client_off back; a buffer that could take more than MAX_BATCH
+// bytes is sized first, so that a client too long for one frame fails before anything is written.
+bool nxg_encode_clients(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
+                        const NxgDispatch* d, uint32_t n_clients, NxgClientFrames* out,
+                        NetidxError* err) {
+    if (!c || !batch || !d || !out || !out->client_off || !d->chan_off) {
+        set_err(err, "null argument");
+        return false;
+    }
+    const uint64_t ne = d->n_entries;
+    const bool f64 = batch->layout == NXG_LAYOUT_F64;
+    if (batch->n_ctl) {
+        set_err(err, "per-client batches encode from columns without control messages (n_ctl = "
+                     "%llu)", (unsigned long long)batch->n_ctl);
+        return false;
+    }
+    if (ne && (!d->ent_row || !batch->id || !batch->fixed ||
+               (!f64 && (!batch->tag || !batch->aux)))) {
+        set_err(err, "null entry array or batch column");
+        return false;
+    }
+    if (batch->mem != NXG_MEM_DEVICE || !is_device_ptr(d->chan_off) ||
+        !is_device_ptr(out->client_off) || (out->out && !is_device_ptr(out->out)) ||
+        (ne && (!is_device_ptr(d->ent_row) || !is_device_ptr(batch->id))) ||
+        (heap && !is_device_ptr(heap))) {
+        set_err(err, "nxg_encode_clients takes device memory only (batch, heap, the dispatch's "
+                     "arrays, out->out and out->client_off)");
+        return false;
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    out->n_bytes = 0;
+    const uint64_t cnt = (uint64_t)n_clients + 1;
+    if (ne == 0) {  // no entries: every payload is empty, and no tile kernel runs
+        HIPCHK(hipMemsetAsync(out->client_off, 0, cnt * 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    const uint64_t nt = nxg_enc_clients_tiles(f64, ne);
+    if (nt >= (1ull << 32)) {
+        set_err(err, "too many entries for one call (%llu)", (unsigned long long)ne);
+        return false;
+    }
+    if (!ensure_tstat(c, nt, err)) return false;
+    const ColsDesc cd = desc_of(batch);
+    const NxgGather g{d->ent_row, ne, d->chan_off, n_clients, out->client_off};
+    std::vector<uint64_t> off(cnt);
+    uint64_t total = 0;
+    auto pass = [&](uint8_t* dout, uint64_t cap) -> bool {
+        DevStatus* st;
+        uint32_t slot;
+        // all-ones first: a chan_off that decreases can make the tiles' walks skip a client, and
+        // an element left unwritten then fails the check below (every message has at least one
+        // byte, so the written offsets decrease exactly where chan_off does)
+        HIPCHK(hipMemsetAsync(out->client_off, 0xff, cnt * 8, c->stream));
+        if (!begin_call(c, &st, &slot, err)) return false;
+        const hipError_t le = nxg_launch_enc_clients(f64, cd, heap, g, dout, cap, c->tstat,
+                                                     c->epoch, st, c->grid_enc_f64,
+                                                     c->grid_enc_gen, c->stream);
+        if (!end_call(c, err)) return false;
+        HIPCHK(le);
+        HIPCHK(hipMemcpyAsync(c->hst + slot, st, sizeof(DevStatus), hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipMemcpyAsync(off.data(), out->client_off, cnt * 8, hipMemcpyDeviceToHost,
+                              c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const DevStatus h = c->hst[slot];
+        if (h.timeout) {
+            set_err(err, "device look-back watchdog expired");
+            return false;
+        }
+        if (h.err_key) {
+            set_err(err, "entry %llu names a row at or past the batch's %llu rows",
+                    (unsigned long long)~h.err_key, (unsigned long long)batch->n_rows);
+            return false;
+        }
+        if (h.err_kind) {
+            if (h.err_kind == NXG_TOO_BIG)
+                set_err(err, "encode failed: a message exceeds MAX_BATCH (%llu bytes) or a size "
+                             "guard (PackError::TooBig)", (unsigned long long)kMaxBatch);
+            else
+                set_err(err, "encode failed: PackError kind %u", h.err_kind);
+            return false;
+        }
+        bool sorted = !(h.irregular & 1u) && off[n_clients] == h.total_bytes;
+        for (uint64_t i = 0; sorted && i < n_clients; i++) sorted = off[i] <= off[i + 1];
+        if (!sorted) {
+            set_err(err, "d->chan_off is not a dispatch's: it must not decrease and must end at "
+                         "d->n_entries (%llu)", (unsigned long long)ne);
+            return false;
+        }
+        total = h.total_bytes;
+        out->n_bytes = total;
+        if (dout && (h.capacity || total > cap)) {
+            set_err(err, "output buffer too small: need %llu bytes, have %llu",
+                    (unsigned long long)total, (unsigned long long)cap);
+            return false;
+        }
+        return true;
+    };
+    // each client's payload goes out as one frame: none may pass MAX_BATCH
+    auto frames_ok = [&]() -> bool {
+        for (uint64_t i = 0; i < n_clients; i++)
+            if (off[i + 1] - off[i] > kMaxBatch) {
+                set_err(err, "client %llu's payload of %llu bytes exceeds MAX_BATCH (%llu): encode "
+                             "that client's rows with nxg_encode_frames",
+                        (unsigned long long)i, (unsigned long long)(off[i + 1] - off[i]),
+                        (unsigned long long)kMaxBatch);
+                return false;
+            }
+        return true;
+    };
+    if (!out->out) return pass(nullptr, 0);
+    if (out->cap_bytes > kMaxBatch) {
+        if (!pass(nullptr, 0) || !frames_ok()) return false;
+        if (total > out->cap_bytes) {
+            set_err(err, "output buffer too small: need %llu bytes, have %llu",
+                    (unsigned long long)total, (unsigned long long)out->cap_bytes);
+            return false;
+        }
+    }
+    return pass(out->out, out->cap_bytes) && frames_ok();
+}
+
 bool nxg_encoded_len(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, uint64_t* len_out,
                      NetidxError* err) {
     return encode_impl(c, in, heap, nullptr, 0, len_out, err);

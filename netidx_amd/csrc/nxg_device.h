@@ -311,6 +311,58 @@ NXG_DEV T block_excl_scan(T v, T* tmp, T* total) {
     return wbase + inc - v;
 }
 
+// ---- per-client offsets of a gathered encode (NxgGather) -------------------------------------
+// The first i in [0, cnt) with a[i] >= x (cnt: none) of a non-decreasing a, by one full wave: 64
+// probes per memory round trip (three round trips cover 2^18 words). Whatever a holds, no index
+// at or past cnt is read.
+NXG_DEV uint64_t wave_lower_bound(const uint64_t* a, uint64_t cnt, uint64_t x) {
+    const uint32_t lane = lane_id();
+    uint64_t lo = 0, hi = cnt;  // a[i] < x below lo, a[i] >= x from hi on
+#pragma unroll 1
+    while (lo < hi) {
+        const uint64_t step = (hi - lo + 63) >> 6;
+        const uint64_t idx = lo + lane * step;
+        const bool p = idx >= hi || a[idx] >= x;
+        const uint64_t m = __ballot(p);
+        const uint32_t first = m ? (uint32_t)__builtin_ctzll(m) : 64u;
+        if (first == 0) break;
+        const uint64_t nh = lo + first * step;
+        lo += (first - 1) * step + 1;
+        if (nh < hi) hi = nh;
+    }
+    return lo;
+}
+
+// client_off[c] = base + the tile-local byte offset of entry chan_off[c], for the clients whose
+// chan_off[c] lies in the tile's entries [e0, e1): c_lo is the first of them, and the waves walk on
+// from there, 64 clients each, while chan_off[c] < e1. The last tile takes every further client
+// too (chan_off[c] == e1 == n_ent: the total; past it: flagged). A run of empty clients gets one
+// offset. prefix(j): the byte offset of the tile's entry j within the tile. Called by every thread
+// of an NT-thread block; plain vector stores; no element past client_off[n_clients] is written.
+template <int NT, typename F>
+NXG_DEV void store_client_offs(const NxgGather& g, uint64_t c_lo, uint64_t e0, uint64_t e1,
+                               bool last, uint64_t base, uint64_t tbytes, DevStatus* st,
+                               F&& prefix) {
+    const uint32_t lane = lane_id();
+    const uint64_t cnt = (uint64_t)g.n_clients + 1;
+#pragma unroll 1
+    for (uint64_t c0 = c_lo + 64ull * (threadIdx.x >> 6);; c0 += NT) {
+        const uint64_t c = c0 + lane;
+        const uint64_t e = c < cnt ? g.chan_off[c] : ~0ull;
+        const bool mine = c < cnt && (last || e < e1);
+        // (e < e0: only under a chan_off that decreases; the client is left to the tile that holds
+        // the entry, so that whatever is stored is that entry's true offset and the host's check of
+        // the offsets finds the decrease)
+        if (mine && e >= e0) {
+            uint64_t o = tbytes;
+            if (e < e1) o = prefix((uint32_t)(e - e0));
+            else if (e > e1) atomicOr(&st->irregular, 1u);
+            g.client_off[c] = base + o;
+        }
+        if (__ballot(mine) != ~0ull) break;
+    }
+}
+
 // ---- UTF-8 (std::str::from_utf8) over an arbitrary byte source -----------------------------
 template <typename Src>
 NXG_DEV bool utf8_valid(const Src& s, uint64_t p, uint64_t n) {

@@ -88,12 +88,30 @@ NXG_DEV uint64_t lookback_selfhelp(const uint64_t* tstat, uint32_t tile, uint32_
         return wave_sum<uint64_t>(b);
     });
 }
+// LDS of the gathered instantiation alone: each thread's byte offset within the tile, and the
+// tile's first client
+NXG_DEV uint32_t* gather_toff() {
+    __shared__ uint32_t a[TPB];
+    return a;
+}
+NXG_DEV uint64_t* gather_clo() {
+    __shared__ uint64_t a[1];
+    return a;
+}
 }  // namespace
 
-__global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
+// The kernel's body. GA: the records are the entries of a dispatch (nxg_encode_clients): n counts
+// entries, entry e is the row g.ent_row[e] of the n_rows-row columns (a row index past them flags
+// the call and takes no bytes), and the tile stores the byte offsets of the clients that start in
+// it. (In the unnamed namespace, so that each instantiation's LDS arrays stay internal to its
+// kernel.)
+namespace {
+template <bool GA>
+NXG_DEV void enc_f64(
     const uint64_t* __restrict__ id, const uint64_t* __restrict__ val, uint64_t n,
     uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ tstat, uint32_t ntiles,
-    uint32_t epoch, DevStatus* __restrict__ st, DevStatus* zst, uint32_t patience) {
+    uint32_t epoch, DevStatus* __restrict__ st, DevStatus* zst, uint32_t patience,
+    uint64_t n_rows, const NxgGather& g) {
     zero_status(zst);
     __shared__ __attribute__((aligned(16))) uint8_t stg[MAXB_ALL];
     __shared__ uint32_t scan_tmp[4];
@@ -103,7 +121,36 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t r0 = (uint64_t)tile * ETILE + (uint64_t)tid * ERPT;
         uint64_t ids[ERPT], vals[ERPT];
-        if (r0 + ERPT <= n) {
+        uint32_t ok = 0;  // GA: bit k: entry r0 + k exists and names a row of the columns
+        if constexpr (GA) {
+            uint64_t rw[ERPT];
+            if (r0 + ERPT <= n) {
+                typedef uint64_t u64x4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+                for (int k = 0; k < ERPT; k += 4) {  // 32 bytes of entries per load
+                    u64x4 a;
+                    __builtin_memcpy(&a, g.ent_row + r0 + k, sizeof a);
+                    rw[k] = a[0]; rw[k + 1] = a[1]; rw[k + 2] = a[2]; rw[k + 3] = a[3];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < ERPT; k++) rw[k] = r0 + k < n ? g.ent_row[r0 + k] : 0;
+            }
+#pragma unroll
+            for (int k = 0; k < ERPT; k++) {
+                const bool in = r0 + k < n;
+                if (in && rw[k] >= n_rows)
+                    atomicMax(reinterpret_cast<unsigned long long*>(&st->err_key),
+                              ~(unsigned long long)(r0 + k));
+                if (in && rw[k] < n_rows) ok |= 1u << k;
+            }
+            // the columns through the indirection (rows ascend within a client: near-coalesced)
+#pragma unroll
+            for (int k = 0; k < ERPT; k++) {
+                ids[k] = (ok >> k) & 1u ? id[rw[k]] : 0;
+                vals[k] = (ok >> k) & 1u ? val[rw[k]] : 0;
+            }
+        } else if (r0 + ERPT <= n) {
 #pragma unroll
             for (int k = 0; k < ERPT; k += 2) {
                 if (NXG_ENC_NT & 1) {
@@ -128,18 +175,45 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
                 vals[k] = r0 + k < n ? val[r0 + k] : 0;
             }
         }
+        // record k of the thread is there (GA: and names a row)
+        auto has = [&](int k) -> bool {
+            if constexpr (GA) return (ok >> k) & 1u;
+            else return r0 + k < n;
+        };
         uint32_t mylen = 0;
 #pragma unroll
-        for (int k = 0; k < ERPT; k++) mylen += (r0 + k < n) ? rec_len(ids[k]) : 0u;
+        for (int k = 0; k < ERPT; k++) mylen += has(k) ? rec_len(ids[k]) : 0u;
         uint32_t tbytes;
         const uint32_t off = block_excl_scan<uint32_t, TPB>(mylen, scan_tmp, &tbytes);
+        if constexpr (GA) {
+            gather_toff()[tid] = off;
+            // the first client that starts at or after this tile's first entry (wave 1, while
+            // wave 0 looks back)
+            if (tid >= 64 && tid < 128) {
+                const uint64_t c = wave_lower_bound(g.chan_off, (uint64_t)g.n_clients + 1,
+                                                    (uint64_t)tile * ETILE);
+                if (lane == 0) gather_clo()[0] = c;
+            }
+        }
         if (tid == 0) st_agent(&tstat[tile], lb_word(tile == 0 ? kFlagInc : kFlagAgg, epoch, tbytes));
 
         // decoupled look-back over tile byte counts (wave 0)
         if (tid < 64) {
             uint64_t base = 0;
             if (tile != 0) {
-                base = lookback_selfhelp(tstat, tile, epoch, id, n, lane, patience);
+                if constexpr (GA)
+                    base = lookback_selfhelp_fn(
+                        tstat, tile, epoch, patience, [&](uint64_t t) -> uint64_t {
+                            const uint64_t q0 = t * ETILE;
+                            uint64_t b = 0;
+                            for (uint64_t e = q0 + lane; e < q0 + ETILE && e < n; e += 64) {
+                                const uint64_t r = g.ent_row[e];
+                                b += r < n_rows ? rec_len(id[r]) : 0u;
+                            }
+                            return wave_sum<uint64_t>(b);
+                        });
+                else
+                    base = lookback_selfhelp(tstat, tile, epoch, id, n, lane, patience);
                 if (lane == 0) st_agent(&tstat[tile], lb_word(kFlagInc, epoch, base + tbytes));
             }
             if (lane == 0) sh_base = base;
@@ -149,7 +223,21 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
         const uint32_t phase = (uint32_t)(base & 15u);
 
         const uint64_t end = base + tbytes;
-        if (base <= kMaxBatch && kMaxBatch < end) {  // the first frame boundary is in this tile
+        if constexpr (GA) {
+            // the clients that start in this tile: their byte offsets (no frame-cut bookkeeping:
+            // each client's payload is its own frame)
+            const uint64_t e0 = (uint64_t)tile * ETILE;
+            store_client_offs<TPB>(
+                g, gather_clo()[0], e0, e0 + ETILE < n ? e0 + ETILE : n, tile == ntiles - 1, base,
+                tbytes, st, [&](uint32_t j) -> uint64_t {
+                    uint64_t o = gather_toff()[j / ERPT];
+                    for (uint32_t q = j - j % ERPT; q < j; q++) {
+                        const uint64_t r = g.ent_row[e0 + q];
+                        o += r < n_rows ? rec_len(id[r]) : 0u;
+                    }
+                    return o;
+                });
+        } else if (base <= kMaxBatch && kMaxBatch < end) {  // the first frame boundary is in this tile
             uint64_t o = base + off;
 #pragma unroll
             for (int k = 0; k < ERPT; k++)
@@ -165,7 +253,7 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
             uint64_t o = base + off;
 #pragma unroll
             for (int k = 0; k < ERPT; k++)
-                if (r0 + k < n) {
+                if (has(k)) {
                     put_rec_global(out, o, ids[k], vals[k]);
                     o += rec_len(ids[k]);
                 }
@@ -173,7 +261,7 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
             uint32_t o = phase + off;
 #pragma unroll
             for (int k = 0; k < ERPT; k++)
-                if (r0 + k < n) o = put_rec(stg, o, ids[k], vals[k]);
+                if (has(k)) o = put_rec(stg, o, ids[k], vals[k]);
             __syncthreads();
             if (tbytes) {
                 const uint64_t gb0 = base & ~15ull;
@@ -202,6 +290,21 @@ __global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
         __syncthreads();
     }
 }
+}  // namespace
+
+__global__ __launch_bounds__(TPB) void nxg_enc_f64_kernel(
+    const uint64_t* __restrict__ id, const uint64_t* __restrict__ val, uint64_t n,
+    uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ tstat, uint32_t ntiles,
+    uint32_t epoch, DevStatus* __restrict__ st, DevStatus* zst, uint32_t patience) {
+    enc_f64<false>(id, val, n, out, cap, tstat, ntiles, epoch, st, zst, patience, 0, NxgGather{});
+}
+__global__ __launch_bounds__(TPB) void nxg_enc_f64_gather_kernel(
+    const uint64_t* __restrict__ id, const uint64_t* __restrict__ val, uint64_t n_rows,
+    NxgGather g, uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ tstat,
+    uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st, DevStatus* zst,
+    uint32_t patience) {
+    enc_f64<true>(id, val, g.n_ent, out, cap, tstat, ntiles, epoch, st, zst, patience, n_rows, g);
+}
 
 uint64_t nxg_enc_f64_tiles(uint64_t n) { return (n + ETILE - 1) / ETILE; }
 
@@ -213,6 +316,21 @@ hipError_t nxg_launch_enc_f64(const uint64_t* id, const uint64_t* val, uint64_t 
     const uint64_t g = grid <= 0 ? nt : (nt < (uint64_t)grid ? nt : (uint64_t)grid);
     hipLaunchKernelGGL(nxg_enc_f64_kernel, dim3(g), dim3(TPB), 0, s, id, val, n, out, cap, tstat,
                        (uint32_t)nt, epoch, st, nxg_take_zero_slot(), nxg_patience);
+    return hipGetLastError();
+}
+
+uint64_t nxg_enc_f64_gather_tiles(uint64_t n_ent) { return nxg_enc_f64_tiles(n_ent); }
+
+hipError_t nxg_launch_enc_f64_gather(const uint64_t* id, const uint64_t* val, uint64_t n_rows,
+                                     const NxgGather& g, uint8_t* out, uint64_t cap,
+                                     uint64_t* tstat, uint32_t epoch, DevStatus* st, int grid,
+                                     hipStream_t s) {
+    const uint64_t nt = nxg_enc_f64_gather_tiles(g.n_ent);
+    if (nt == 0) return hipSuccess;
+    const uint64_t gr = grid <= 0 ? nt : (nt < (uint64_t)grid ? nt : (uint64_t)grid);
+    hipLaunchKernelGGL(nxg_enc_f64_gather_kernel, dim3(gr), dim3(TPB), 0, s, id, val, n_rows, g,
+                       out, cap, tstat, (uint32_t)nt, epoch, st, nxg_take_zero_slot(),
+                       nxg_patience);
     return hipGetLastError();
 }
 

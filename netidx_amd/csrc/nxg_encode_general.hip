@@ -289,6 +289,14 @@ NXG_DEV uint64_t row_msg_len(const ColsDesc& c, uint64_t r, bool arch, WalkStack
 
 }  // namespace
 
+namespace {
+// LDS of the gathered instantiation alone: the tile's first client
+NXG_DEV uint64_t* gather_clo() {
+    __shared__ uint64_t a[1];
+    return a;
+}
+}  // namespace
+
 // exclusive prefix of ctl_len into ctl_pre[0..n_ctl] (one workgroup)
 __global__ __launch_bounds__(TPB) void nxg_enc_ctl_scan_kernel(ColsDesc c, uint64_t* ctl_pre) {
     __shared__ uint64_t tmp[4];
@@ -305,15 +313,21 @@ __global__ __launch_bounds__(TPB) void nxg_enc_ctl_scan_kernel(ColsDesc c, uint6
 }
 
 // The rows kernel's body. WR: Write mode (To::Write rows from c.wflags / c.wid; arch_base is 0).
+// GA: the rows are the entries of a dispatch (nxg_encode_clients; no control messages, no archive
+// mode, no frame-cut bookkeeping): n counts entries, entry e is the row g.ent_row[e] of the
+// c.n_rows-row columns (a row index past them flags the call, is sized as zero bytes and never
+// indexes a column), and the tile stores the byte offsets of the clients that start in it. The
+// tile's rows sit in LDS over the staging until the staging pass begins; after that a row index
+// comes from g.ent_row again.
 // (In the unnamed namespace, so that each instantiation's LDS arrays stay internal to its kernel.)
 namespace {
-template <bool WR>
+template <bool WR, bool GA>
 NXG_DEV void enc_rows(
     ColsDesc c, const uint8_t* __restrict__ heap, uint8_t* __restrict__ out, uint64_t cap,
     const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
     uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
-    DevStatus* zst, uint64_t arch_base, uint32_t patience) {
-    const bool arch = arch_base != 0;
+    DevStatus* zst, uint64_t arch_base, uint32_t patience, const NxgGather& g) {
+    const bool arch = !GA && arch_base != 0;
     zero_status(zst);
     __shared__ uint64_t tmp[4];
     __shared__ uint64_t sh_base;
@@ -331,17 +345,62 @@ NXG_DEV void enc_rows(
     static_assert(GSTG < 65536, "staging offsets fit 16 bits");
     const uint32_t tid = threadIdx.x, lane = tid & 63;
     WalkStack* const stk = &wstk[tid >> 6];
-    const uint64_t n = c.n_rows;
+    const uint64_t n = GA ? g.n_ent : c.n_rows;
+    // GA, over the staging: the rows of the tile's entries (~0: none, or past the columns) until
+    // the staging pass, and behind them each thread's byte offset within a tile that is not staged
+    uint64_t* const row_lds = reinterpret_cast<uint64_t*>(stg);
+    uint64_t* const toff_lds = row_lds + GTILE;
+    static_assert((GTILE + TPB) * 8 <= GSTG, "the gathered rows fit the staging");
+    // the thread's GRPT entries from tile-relative entry q0 on: their rows (one 32-byte load),
+    // the row's tag (0 where there is none)
+    uint64_t nrw[GRPT];
+    auto load_rows = [&](uint64_t q0) {
+        if (q0 + GRPT <= n) {
+            typedef uint64_t u64x4 __attribute__((ext_vector_type(4)));
+            static_assert(GRPT == 4, "one 32-byte load of entries");
+            u64x4 a;
+            __builtin_memcpy(&a, g.ent_row + q0, sizeof a);
+            nrw[0] = a[0]; nrw[1] = a[1]; nrw[2] = a[2]; nrw[3] = a[3];
+        } else {
+#pragma unroll
+            for (int k = 0; k < GRPT; k++) nrw[k] = q0 + k < n ? g.ent_row[q0 + k] : ~0ull;
+        }
+#pragma unroll
+        for (int k = 0; k < GRPT; k++) {
+            if (q0 + k < n && nrw[k] >= c.n_rows) {
+                atomicMax(reinterpret_cast<unsigned long long*>(&st->err_key),
+                          ~(unsigned long long)(q0 + k));
+                nrw[k] = ~0ull;
+            }
+            if (q0 + k >= n) nrw[k] = ~0ull;
+        }
+    };
     // the tags of the thread's rows in its next tile, loaded during this tile's look-back
     uint32_t ntg[GRPT];
+    if constexpr (GA) load_rows((uint64_t)blockIdx.x * GTILE + (uint64_t)tid * GRPT);
 #pragma unroll
     for (int k = 0; k < GRPT; k++) {
         const uint64_t r = (uint64_t)blockIdx.x * GTILE + (uint64_t)tid * GRPT + k;
-        ntg[k] = r < n ? c.tag[r] : 0u;
+        if constexpr (GA) ntg[k] = nrw[k] != ~0ull ? c.tag[nrw[k]] : 0u;
+        else ntg[k] = r < n ? c.tag[r] : 0u;
     }
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint64_t rt = (uint64_t)tile * GTILE;
         const uint64_t r0 = rt + (uint64_t)tid * GRPT;
+        // the row of the tile's entry rl (GA: from LDS, until the staging pass)
+        auto row_of = [&](uint32_t rl) -> uint64_t {
+            if constexpr (GA) return row_lds[rl];
+            else return rt + rl;
+        };
+        if constexpr (GA) {
+#pragma unroll
+            for (int k = 0; k < GRPT; k++) row_lds[tid * GRPT + k] = nrw[k];
+            // the first client that starts at or after this tile's first entry (wave 1)
+            if (tid >= 64 && tid < 128) {
+                const uint64_t cl = wave_lower_bound(g.chan_off, (uint64_t)g.n_clients + 1, rt);
+                if (lane == 0) gather_clo()[0] = cl;
+            }
+        }
         ESTAMP(0);
         // 1. classify by tag and bucket the rows (wave-ballot counting sort in LDS); a wave then
         //    writes and sizes one class at a time
@@ -356,8 +415,10 @@ NXG_DEV void enc_rows(
 #pragma unroll
             for (int k = 0; k < GRPT; k++) {
                 const uint64_t r = r0 + k;
+                static_assert(!GA || NXG_ENC_PF, "the gathered tags come from the prefetch");
                 const uint32_t tg = NXG_ENC_PF ? ntg[k] : r < n ? c.tag[r] : 0u;
-                cls[k] = r < n ? (arch && tg == 0x40u ? (uint32_t)CLS_SCAL : value_class(tg)) : NCLS;
+                const bool there = GA ? nrw[k] != ~0ull : r < n;
+                cls[k] = there ? (arch && tg == 0x40u ? (uint32_t)CLS_SCAL : value_class(tg)) : NCLS;
                 pos[k] = 0;
 #pragma unroll
                 for (uint32_t q = 0; q < NCLS; q++) {
@@ -399,7 +460,8 @@ NXG_DEV void enc_rows(
         for (int k = 0; k < GRPT; k++) {
             const uint64_t r = r0 + k;
             const uint32_t tg = NXG_ENC_PF ? ntg[k] : r < n ? c.tag[r] : 0u;
-            cls[k] = r < n ? (arch && tg == 0x40u ? (uint32_t)CLS_SCAL : value_class(tg)) : NCLS;
+            const bool there = GA ? nrw[k] != ~0ull : r < n;
+            cls[k] = there ? (arch && tg == 0x40u ? (uint32_t)CLS_SCAL : value_class(tg)) : NCLS;
             pos[k] = 0;
 #pragma unroll
             for (uint32_t q = 0; q < NCLS; q++) {
@@ -436,7 +498,7 @@ NXG_DEV void enc_rows(
         // 2. message lengths, class by class. Each thread's next entry's slot and id are loaded
         //    while it sizes the current one (NXG_ENC_PF: two memory round trips in flight)
         auto size_one = [&](uint32_t rl, Slot v, uint64_t idv, uint64_t widv, uint32_t) {
-            const uint64_t r = rt + rl;
+            const uint64_t r = row_of(rl);
             uint64_t vlen = 0;
             uint32_t err = 0;
             bool gen = false;
@@ -478,6 +540,9 @@ NXG_DEV void enc_rows(
             if (err) atomicMax(&st->err_kind, err);
             len_lds[rl] = err ? 0u : (uint32_t)ml;
         };
+#if !NXG_ENC_KEEP
+        static_assert(!GA, "the gathered rows are loaded by the NXG_ENC_KEEP loads");
+#endif
 #if NXG_ENC_KEEP
         uint32_t k_rl[4];
         Slot k_v[4];
@@ -488,8 +553,8 @@ NXG_DEV void enc_rows(
         for (int j = 0; j < GRPT; j++) {
             const uint32_t e = tid + (uint32_t)j * TPB;
             k_rl[j] = e < ne ? lst_row[e] : 0u;
-            k_v[j] = e < ne ? get_slot(c, true, rt + k_rl[j]) : Slot{0, 0, 0};
-            k_id[j] = e < ne ? c.id[rt + k_rl[j]] : 0ull;
+            k_v[j] = e < ne ? get_slot(c, true, row_of(k_rl[j])) : Slot{0, 0, 0};
+            k_id[j] = e < ne ? c.id[row_of(k_rl[j])] : 0ull;
             k_w[j] = 0ull;
             k_f[j] = 0u;
             if constexpr (WR) {
@@ -560,8 +625,14 @@ NXG_DEV void enc_rows(
                     tstat, tile, epoch, patience, [&](uint64_t t) -> uint64_t {
                         const uint64_t q0 = t * GTILE;
                         uint64_t b = 0;
-                        for (uint64_t r = q0 + lane; r < q0 + GTILE && r < n; r += 64)
-                            b += row_msg_len<WR>(c, r, arch, &wstk[0]);
+                        for (uint64_t r = q0 + lane; r < q0 + GTILE && r < n; r += 64) {
+                            if constexpr (GA) {
+                                const uint64_t rw = g.ent_row[r];
+                                if (rw < c.n_rows) b += row_msg_len<WR>(c, rw, arch, &wstk[0]);
+                            } else {
+                                b += row_msg_len<WR>(c, r, arch, &wstk[0]);
+                            }
+                        }
                         return wave_sum<uint64_t>(b);
                     });
 #endif
@@ -571,6 +642,9 @@ NXG_DEV void enc_rows(
             if (lane == 0) sh_base = base;
         };
         const bool stage = out && c.n_ctl == 0 && tot <= (uint64_t)(GSTG - 32);
+        if constexpr (GA) {
+            if (!stage) toff_lds[tid] = off;  // (a staged tile: off_lds has every entry's offset)
+        }
         if (stage) {
             {
                 uint32_t o = (uint32_t)off;
@@ -582,7 +656,6 @@ NXG_DEV void enc_rows(
             }
             __syncthreads();
             auto stage_one = [&](uint32_t rl, Slot v, uint64_t idv, uint64_t widv, uint32_t fl) {
-                const uint64_t r = rt + rl;
                 const uint32_t len = len_lds[rl];
                 if (!len) return;
                 Out w{stg, off_lds[rl]};
@@ -617,8 +690,11 @@ NXG_DEV void enc_rows(
                 case CLS_SCAL: scalar_write(v, heap, w); break;
                 default: break;
                 }
-                one_lane_at_a_time(cls_lds[rl] == CLS_GEN,
-                                   [&] { value_write(c, heap, true, r, w, stk); });
+                one_lane_at_a_time(cls_lds[rl] == CLS_GEN, [&] {
+                    // (GA: the staging has replaced the rows in LDS; len != 0: the row is valid)
+                    const uint64_t r = GA ? g.ent_row[rt + rl] : rt + rl;
+                    value_write(c, heap, true, r, w, stk);
+                });
                 if constexpr (WR) w.var(widv);
             };
 #if NXG_ENC_KEEP
@@ -651,8 +727,12 @@ NXG_DEV void enc_rows(
         }
         if (NXG_ENC_PF) {  // the next tile's tags: their round trip overlaps the look-back
             const uint64_t rn = (uint64_t)(tile + gridDim.x) * GTILE + (uint64_t)tid * GRPT;
+            if constexpr (GA) load_rows(rn);
 #pragma unroll
-            for (int k = 0; k < GRPT; k++) ntg[k] = rn + k < n ? c.tag[rn + k] : 0u;
+            for (int k = 0; k < GRPT; k++) {
+                if constexpr (GA) ntg[k] = nrw[k] != ~0ull ? c.tag[nrw[k]] : 0u;
+                else ntg[k] = rn + k < n ? c.tag[rn + k] : 0u;
+            }
         }
         // 3b. the tile's base: look-back over the tiles' byte counts (wave 0; running it while
         //     the other waves stage measured slower, 0.281 vs 0.245 ms)
@@ -661,11 +741,21 @@ NXG_DEV void enc_rows(
         __syncthreads();
         ESTAMP(5);
         const uint64_t tbase = sh_base + arch_base;
+        if constexpr (GA) {
+            // the clients that start in this tile: their byte offsets
+            store_client_offs<TPB>(g, gather_clo()[0], rt, rt + GTILE < n ? rt + GTILE : n,
+                                   tile == ntiles - 1, tbase, tot, st, [&](uint32_t j) -> uint64_t {
+                                       if (stage) return off_lds[j];
+                                       uint64_t o = toff_lds[j / GRPT];
+                                       for (uint32_t q = j - j % GRPT; q < j; q++) o += len_lds[q];
+                                       return o;
+                                   });
+        }
         if (stage && tbase + tot <= cap) {
             // 4b. the staging out as aligned nontemporal 16-byte stores: global block g holds the
             //     staged bytes from g - tbase; the two edge blocks (shared with the neighbours)
             //     by bytes
-            if (!WR && !arch && tbase <= kMaxBatch && kMaxBatch < tbase + tot) {
+            if (!WR && !GA && !arch && tbase <= kMaxBatch && kMaxBatch < tbase + tot) {
                 uint64_t o = tbase + off;
 #pragma unroll
                 for (int k = 0; k < GRPT; k++) {
@@ -706,13 +796,14 @@ NXG_DEV void enc_rows(
             uint64_t rpos = tbase + off;  // rows-only prefix
 #pragma unroll 1  // (a large body with a lane-serial walk: not worth unrolling)
             for (int k = 0; k < GRPT; k++) {
-                const uint64_t r = r0 + k;
                 const uint64_t Lk = len_lds[tid * GRPT + k];
-                if (r < n && row_off) row_off[r] = rpos;  // ctl placement needs every row's base
-                if (r < n && Lk && out) {
+                // (GA: Lk != 0 only for an entry whose row was checked against c.n_rows)
+                const uint64_t r = GA ? (r0 + k < n && Lk ? g.ent_row[r0 + k] : ~0ull) : r0 + k;
+                if (!GA && r < n && row_off) row_off[r] = rpos;  // ctl placement needs every row's base
+                if ((GA ? r != ~0ull : r < n) && Lk && out) {
                     uint64_t pos = rpos;
-                    if (c.n_ctl) pos += ctl_pre[ctl_upto(c.ctl_row, c.n_ctl, r)];
-                    if (!WR && !arch) note_split(st, pos, Lk);
+                    if (!GA && c.n_ctl) pos += ctl_pre[ctl_upto(c.ctl_row, c.n_ctl, r)];
+                    if (!WR && !GA && !arch) note_split(st, pos, Lk);
                     if (pos + Lk > cap) {
                         atomicOr(&st->capacity, 1u);
                     } else {
@@ -753,16 +844,23 @@ __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_kernel(
     const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
     uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
     DevStatus* zst, uint64_t arch_base, uint32_t patience) {
-    enc_rows<false>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst, arch_base,
-                    patience);
+    enc_rows<false, false>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst,
+                           arch_base, patience, NxgGather{});
 }
 __global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_writes_kernel(
     ColsDesc c, const uint8_t* __restrict__ heap, uint8_t* __restrict__ out, uint64_t cap,
     const uint64_t* __restrict__ ctl_pre, uint64_t* __restrict__ row_off,
     uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch, DevStatus* __restrict__ st,
     DevStatus* zst, uint64_t arch_base, uint32_t patience) {
-    enc_rows<true>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst, arch_base,
-                   patience);
+    enc_rows<true, false>(c, heap, out, cap, ctl_pre, row_off, tstat, ntiles, epoch, st, zst,
+                          arch_base, patience, NxgGather{});
+}
+__global__ __launch_bounds__(TPB, NXG_ENC_OCC) void nxg_enc_rows_gather_kernel(
+    ColsDesc c, const uint8_t* __restrict__ heap, NxgGather g, uint8_t* __restrict__ out,
+    uint64_t cap, uint64_t* __restrict__ tstat, uint32_t ntiles, uint32_t epoch,
+    DevStatus* __restrict__ st, DevStatus* zst, uint32_t patience) {
+    enc_rows<false, true>(c, heap, out, cap, nullptr, nullptr, tstat, ntiles, epoch, st, zst, 0,
+                          patience, g);
 }
 
 __global__ __launch_bounds__(TPB) void nxg_enc_ctl_write_kernel(
@@ -823,6 +921,21 @@ hipError_t nxg_launch_enc_general(const ColsDesc& cd, const uint8_t* heap, uint8
         hipLaunchKernelGGL(nxg_enc_ctl_write_kernel, dim3((unsigned)(nb < 1024 ? nb : 1024)),
                            dim3(TPB), 0, s, cd, heap, out, cap, ctl_pre, row_off, st, st);
     }
+    return hipGetLastError();
+}
+
+uint64_t nxg_enc_rows_gather_tiles(uint64_t n_ent) { return nxg_enc_general_tiles(n_ent); }
+
+// cols: the batch's columns (n_ctl == 0); the entries and the client offsets in `g`
+hipError_t nxg_launch_enc_rows_gather(const ColsDesc& cd, const uint8_t* heap, const NxgGather& g,
+                                      uint8_t* out, uint64_t cap, uint64_t* tstat, uint32_t epoch,
+                                      DevStatus* st, int grid, hipStream_t s) {
+    if (cd.n_ctl) return hipErrorInvalidValue;
+    const uint64_t nt = nxg_enc_rows_gather_tiles(g.n_ent);
+    if (nt == 0) return hipSuccess;
+    const uint64_t gr = grid <= 0 ? nt : (nt < (uint64_t)grid ? nt : (uint64_t)grid);
+    hipLaunchKernelGGL(nxg_enc_rows_gather_kernel, dim3(gr), dim3(TPB), 0, s, cd, heap, g, out,
+                       cap, tstat, (uint32_t)nt, epoch, st, nxg_take_zero_slot(), nxg_patience);
     return hipGetLastError();
 }
 

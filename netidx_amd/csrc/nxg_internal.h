@@ -424,6 +424,35 @@ hipError_t nxg_launch_share_bounds(const ColsDesc& src, uint64_t r0, uint64_t r1
 hipError_t nxg_launch_share_copy(const ColsDesc& src, const ColsDesc& dst, uint64_t r0,
                                  uint64_t nr, uint64_t c0, uint64_t nc, uint64_t k0, uint64_t nk,
                                  uint64_t* hb, hipStream_t s);
+// per-client encode (nxg_encode_clients): the tile encoders over a dispatch's entry list. Entry e
+// is the row ent_row[e] of the columns; client c's payload starts at the byte offset of entry
+// chan_off[c], stored to client_off[c] by the tile that holds the entry (the last tile also
+// stores the total for every chan_off[c] >= n_ent). DevStatus of a gathered encode: err_key =
+// ~(the first entry whose row is >= the batch's n_rows) (atomicMax; 0: none), irregular bit 0 = a
+// chan_off past n_ent.
+struct NxgGather {
+    const uint64_t* ent_row;
+    uint64_t n_ent;
+    const uint64_t* chan_off;  // [n_clients + 1]
+    uint32_t n_clients;
+    uint64_t* client_off;      // [n_clients + 1]
+};
+uint64_t nxg_enc_f64_gather_tiles(uint64_t n_ent);
+hipError_t nxg_launch_enc_f64_gather(const uint64_t* id, const uint64_t* val, uint64_t n_rows,
+                                     const NxgGather& g, uint8_t* out, uint64_t cap,
+                                     uint64_t* tstat, uint32_t epoch, DevStatus* st, int grid,
+                                     hipStream_t s);
+uint64_t nxg_enc_rows_gather_tiles(uint64_t n_ent);
+hipError_t nxg_launch_enc_rows_gather(const ColsDesc& cols, const uint8_t* heap,
+                                      const NxgGather& g, uint8_t* out, uint64_t cap,
+                                      uint64_t* tstat, uint32_t epoch, DevStatus* st, int grid,
+                                      hipStream_t s);
+// the layout's gathered encoder (nxg_encode_clients.hip) and its tiles (= tstat words)
+uint64_t nxg_enc_clients_tiles(bool f64, uint64_t n_ent);
+hipError_t nxg_launch_enc_clients(bool f64, const ColsDesc& cols, const uint8_t* heap,
+                                  const NxgGather& g, uint8_t* out, uint64_t cap, uint64_t* tstat,
+                                  uint32_t epoch, DevStatus* st, int grid_f64, int grid_gen,
+                                  hipStream_t s);
 int nxg_occupancy_enc_f64();
 int nxg_occupancy_enc_general();
 
