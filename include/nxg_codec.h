@@ -963,6 +963,79 @@ bool nxg_encode_clients(NxgCtx* ctx, const NxgColumns* batch, const uint8_t* hea
                         const NxgDispatch* d, uint32_t n_clients, NxgClientFrames* out,
                         NetidxError* err);
 
+/* ---- the value table: `pbl.current = v` (publisher/mod.rs:796, 809) and a subscription's `last`
+ * The routing calls read the connection's values from const device columns and report which row
+ * became current (NxgDispatch.last_row[slot] = 1 + row, 0: unchanged). These calls move the values
+ * forward on the device: slot s takes the value of batch row src_row[s] - 1, with its text /
+ * Decimal / Abstract bytes copied into the table's heap and its Array / Map / Error(Value) subtree
+ * copied into the table's child columns, `fixed` re-based. The arrays are the caller's (device
+ * memory); tag NULL is an all-F64 table (NxgPubTable.cur_tag == NULL), of which only `fixed` is
+ * used. The table's columns are what NxgPubTable.cur_* and NxgColumns children expect.
+ *
+ * The table appends: a call writes its payload at heap_used / child_used and advances them. A
+ * replaced value's payload stays where it is and leaves heap_live / child_live (sized by walking
+ * it). Payloads are packed without padding in slot order, each value's in walk order: a container's
+ * elements contiguous, blocks handed out in depth-first preorder, whatever the source layout. The
+ * layout depends on the call sequence only. Source rows may share children, lie in any order and be
+ * named by several slots.
+ *
+ * nxg_value_table_init   every slot Value::Null (tag 16, fixed 0, aux 0; an F64 table: fixed 0),
+ *                        counters 0.
+ * nxg_value_table_apply  in place. src_row: n_slots device words (NxgDispatch.last_row as it is).
+ *                        `heap`, `heap_len`: the batch's payload bytes (a decoded frame: the frame).
+ *                        An F64-layout batch has tag 9, aux 0. An F64 table takes a MIXED batch
+ *                        whose selected rows all have tag 9 (otherwise NXG_NOT_F64 in the message).
+ * nxg_value_table_rebuild  writes dst (its own arrays, dst->n_slots >= src->n_slots, the same kind
+ *                        as src): selected slots from the batch, the others from src, slots past
+ *                        src's Null. Afterwards heap_used == heap_live, child_used == child_live.
+ *                        batch and src_row may be NULL (compaction, growth). The same kernels as
+ *                        apply, the source chosen per slot.
+ * nxg_value_table_set_unsubscribed  the n named slots (device u32) become NXG_TAG_UNSUBSCRIBED,
+ *                        fixed 0, aux 0; their old payload leaves the live counts, a slot named
+ *                        twice once. Called after apply, as the reference sets `last`.
+ *
+ * All or nothing: everything is validated in a sizing pass before the first write. Refused, with
+ * the lowest refused slot and its cause in the message whatever the scheduling: src_row[s] - 1 >=
+ * batch->n_rows; a tag outside 0..27 and NXG_TAG_UNSUBSCRIBED; a payload outside [0, heap_len) (for
+ * a value the table holds: heap_used); a child range outside batch->n_children (child_used); a
+ * container with elements but no child columns; a value at a level past NXG_MAX_DEPTH
+ * (NXG_MAX_DEPTH containers around a scalar are the deepest). If the appended payload does not fit,
+ * the call returns false with NXG_CAPACITY in the message and *out holds the exact needs and the
+ * live totals the table would have: what a rebuild into other arrays must hold. After any false
+ * return the table's arrays and counters are what they were, and no element at or past a capacity
+ * is ever written. Synchronous, one read-back per call (a second pass, before any write, only when
+ * the slots name more heap-borne values than the batch has rows and children); a ctx with async
+ * work pending is refused. The table's arrays must not overlap the batch, its heap, src_row (or,
+ * for rebuild, src): checked on the host. */
+typedef struct NxgValueTable {
+    uint64_t n_slots;
+    uint8_t* tag;      /* [n_slots]; NULL: an all-F64 table */
+    uint64_t* fixed;   /* [n_slots] */
+    uint32_t* aux;     /* [n_slots]; NULL only when tag is NULL */
+    uint8_t* heap;     /* text / Decimal / Abstract payloads */
+    uint64_t cap_bytes;
+    uint8_t* ctag;     /* child columns, [cap_children] each */
+    uint64_t* cfixed;
+    uint32_t* caux;
+    uint64_t cap_children;
+    /* kept by the calls, host memory */
+    uint64_t heap_used, heap_live, child_used, child_live;
+} NxgValueTable;
+typedef struct NxgValueApply { /* written by the call */
+    uint64_t n_applied;                 /* slots with src_row != 0 */
+    uint64_t need_bytes, need_children; /* payload of the new values */
+    uint64_t live_bytes, live_children; /* what the table holds after the call */
+} NxgValueApply;
+bool nxg_value_table_init(NxgCtx* ctx, NxgValueTable* t, NetidxError* err);
+bool nxg_value_table_apply(NxgCtx* ctx, NxgValueTable* t, const NxgColumns* batch,
+                           const uint8_t* heap, uint64_t heap_len, const uint64_t* src_row,
+                           NxgValueApply* out, NetidxError* err);
+bool nxg_value_table_rebuild(NxgCtx* ctx, const NxgValueTable* src, const NxgColumns* batch,
+                             const uint8_t* heap, uint64_t heap_len, const uint64_t* src_row,
+                             NxgValueTable* dst, NxgValueApply* out, NetidxError* err);
+bool nxg_value_table_set_unsubscribed(NxgCtx* ctx, NxgValueTable* t, const uint32_t* slot,
+                                      uint64_t n, NetidxError* err);
+
 /* ---- archive batches: replaces <GPooled<Vec<BatchItem>> as Pack>::decode ------------------
  * (netidx-archive/src/logfile/reader.rs:449/475 over logfile/mod.rs:150-205 BatchItem and
  * netidx/src/subscriber/mod.rs:154-177 Event). `buf` (device memory, `len` bytes) starts with the

@@ -181,6 +181,24 @@ class NxgPubTable(C.Structure):
                 ("cur_caux", C.c_void_p)]
 
 
+class NxgValueTable(C.Structure):
+    _fields_ = [("n_slots", C.c_uint64), ("tag", C.c_void_p), ("fixed", C.c_void_p),
+                ("aux", C.c_void_p), ("heap", C.c_void_p), ("cap_bytes", C.c_uint64),
+                ("ctag", C.c_void_p), ("cfixed", C.c_void_p), ("caux", C.c_void_p),
+                ("cap_children", C.c_uint64), ("heap_used", C.c_uint64),
+                ("heap_live", C.c_uint64), ("child_used", C.c_uint64),
+                ("child_live", C.c_uint64)]
+
+
+class NxgValueApply(C.Structure):
+    _fields_ = [("n_applied", C.c_uint64), ("need_bytes", C.c_uint64),
+                ("need_children", C.c_uint64), ("live_bytes", C.c_uint64),
+                ("live_children", C.c_uint64)]
+
+    def dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class NxgCtlMsg(C.Structure):
     _fields_ = [("msg_len", C.c_uint64), ("variant", C.c_uint32), ("permissions", C.c_uint32),
                 ("id", C.c_uint64), ("path_off", C.c_uint64), ("path_len", C.c_uint64),
@@ -342,6 +360,19 @@ SIGNATURES = {
     "nxg_encode_clients": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
                                       C.POINTER(NxgDispatch), C.c_uint32,
                                       C.POINTER(NxgClientFrames), C.POINTER(NetidxError)]),
+    "nxg_value_table_init": (C.c_bool, [C.c_void_p, C.POINTER(NxgValueTable),
+                                        C.POINTER(NetidxError)]),
+    "nxg_value_table_apply": (C.c_bool, [C.c_void_p, C.POINTER(NxgValueTable),
+                                         C.POINTER(NxgColumns), C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.POINTER(NxgValueApply),
+                                         C.POINTER(NetidxError)]),
+    "nxg_value_table_rebuild": (C.c_bool, [C.c_void_p, C.POINTER(NxgValueTable),
+                                           C.POINTER(NxgColumns), C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.POINTER(NxgValueTable),
+                                           C.POINTER(NxgValueApply), C.POINTER(NetidxError)]),
+    "nxg_value_table_set_unsubscribed": (C.c_bool, [C.c_void_p, C.POINTER(NxgValueTable),
+                                                    C.c_void_p, C.c_uint64,
+                                                    C.POINTER(NetidxError)]),
     "nxg_zstd_dict_new": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_uint64,
                                        C.POINTER(NetidxError)]),
     "nxg_zstd_dict_free": (None, [C.c_void_p]),
@@ -1412,6 +1443,160 @@ class PubTable:
                            p(self.client), self.n_clients, p(self.cur_tag), p(self.cur_fixed),
                            p(self.cur_aux), p(self.cur_heap), p(self.cur_ctag),
                            p(self.cur_cfixed), p(self.cur_caux))
+
+
+class ValueCapacity(CodecError):
+    """An apply or rebuild whose payload does not fit (NXG_CAPACITY); the table is unchanged.
+    `need_bytes` / `need_children`: the new values' payload; `live_bytes` / `live_children`: what
+    the table would hold, i.e. what a rebuild into other arrays needs."""
+
+    def __init__(self, msg, res):
+        super().__init__(msg)
+        self.res = res
+        for k, v in res.items():
+            setattr(self, k, v)
+
+
+class ValueTable:
+    """A device-resident table of values (NxgValueTable): slot -> value in the columnar form, with
+    payload bytes in a heap and container elements in child columns that the table owns (torch
+    tensors). `f64`: only `fixed` (NxgPubTable.cur_tag == NULL). `tensors`: caller-made arrays
+    (tag, fixed, aux, heap, ctag, cfixed, caux) instead of fresh ones -- they may be longer than
+    the stated capacities (the tests' guard bands)."""
+
+    ARRAYS = (("tag", "uint8", "slots"), ("fixed", "int64", "slots"), ("aux", "int32", "slots"),
+              ("heap", "uint8", "bytes"), ("ctag", "uint8", "children"),
+              ("cfixed", "int64", "children"), ("caux", "int32", "children"))
+
+    def __init__(self, codec, n_slots, cap_bytes=0, cap_children=0, f64=False, device="cuda",
+                 tensors=None):
+        import torch
+        self.codec, self.f64, self.device = codec, bool(f64), torch.device(device)
+        self.caps = {"slots": int(n_slots), "bytes": 0 if f64 else int(cap_bytes),
+                     "children": 0 if f64 else int(cap_children)}
+        self.t = {}
+        for name, dt, kind in self.ARRAYS:
+            if f64 and name != "fixed":
+                self.t[name] = None
+            elif tensors is not None:
+                self.t[name] = tensors[name]
+            else:
+                self.t[name] = torch.zeros(max(self.caps[kind], 1), dtype=getattr(torch, dt),
+                                           device=self.device)
+        self.s = NxgValueTable()
+        self.s.n_slots = self.caps["slots"]
+        self.s.cap_bytes, self.s.cap_children = self.caps["bytes"], self.caps["children"]
+        for name, _, _ in self.ARRAYS:
+            setattr(self.s, name, _ptr(self.t[name]).value)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)  # the codec runs on its own stream
+
+    n_slots = property(lambda self: int(self.s.n_slots))
+    heap_used = property(lambda self: int(self.s.heap_used))
+    heap_live = property(lambda self: int(self.s.heap_live))
+    child_used = property(lambda self: int(self.s.child_used))
+    child_live = property(lambda self: int(self.s.child_live))
+
+    def counters(self):
+        return (self.heap_used, self.heap_live, self.child_used, self.child_live)
+
+    def init(self):
+        err = NetidxError()
+        _check(lib().nxg_value_table_init(self.codec.ctx, C.byref(self.s), C.byref(err)), err)
+        return self
+
+    @staticmethod
+    def _finish(ok, err, res):
+        if not ok:
+            msg = err.msg.decode() if err.msg else "unknown error"
+            lib().nxg_error_free(C.byref(err))
+            raise (ValueCapacity(msg, res.dict()) if "NXG_CAPACITY" in msg else CodecError(msg))
+        return res.dict()
+
+    def apply(self, batch, src_row, heap=None, heap_len=None):
+        """Slot s takes the value of batch row src_row[s] - 1 (src_row: n_slots device words,
+        Dispatch.last_row as it is). `heap`: the batch's payload bytes (a device tensor; for a
+        decoded frame the frame). Returns the NxgValueApply as a dict; ValueCapacity when the
+        payload does not fit, CodecError for a refused slot -- the table is unchanged then."""
+        if heap_len is None:
+            heap_len = 0 if heap is None else heap.numel()
+        res, err = NxgValueApply(), NetidxError()
+        ok = lib().nxg_value_table_apply(self.codec.ctx, C.byref(self.s), C.byref(batch.s),
+                                         _heap_ptr(heap), heap_len, _ptr(src_row),
+                                         C.byref(res), C.byref(err))
+        return self._finish(ok, err, res)
+
+    def rebuild(self, dst, batch=None, src_row=None, heap=None, heap_len=None):
+        """`dst` (another ValueTable, at least as many slots) takes this table's values, the
+        selected slots the batch's: compaction, growth, or the apply that did not fit."""
+        if heap_len is None:
+            heap_len = 0 if heap is None else heap.numel()
+        res, err = NxgValueApply(), NetidxError()
+        ok = lib().nxg_value_table_rebuild(
+            self.codec.ctx, C.byref(self.s), C.byref(batch.s) if batch is not None else None,
+            _heap_ptr(heap), heap_len, _ptr(src_row), C.byref(dst.s), C.byref(res),
+            C.byref(err))
+        return self._finish(ok, err, res)
+
+    def set_unsubscribed(self, slots):
+        """The named slots (an int32 device tensor, or a list) become Event::Unsubscribed."""
+        import torch
+        if not hasattr(slots, "data_ptr"):
+            slots = torch.as_tensor(np.array(slots, dtype=np.uint32).view(np.int32)).to(
+                self.device)
+            torch.cuda.synchronize(self.device)
+        err = NetidxError()
+        _check(lib().nxg_value_table_set_unsubscribed(self.codec.ctx, C.byref(self.s),
+                                                      _ptr(slots) if slots.numel() else None,
+                                                      slots.numel(), C.byref(err)), err)
+
+    def as_pub_columns(self):
+        """(cur_tag, cur_fixed, cur_aux, cur_heap, cur_ctag, cur_cfixed, cur_caux): the tensors a
+        PubTable's current values are (None where the table has none)."""
+        n = self.n_slots
+        if self.f64:
+            return (None, self.t["fixed"][:n], None, None, None, None, None)
+        k = self.child_used
+        kids = tuple(self.t[x][:k] if k else None for x in ("ctag", "cfixed", "caux"))
+        return (self.t["tag"][:n], self.t["fixed"][:n], self.t["aux"][:n],
+                self.t["heap"] if self.caps["bytes"] else None) + kids
+
+    def pub_table(self, slot_of_id, slot_client_off, client, n_clients):
+        """A PubTable over these arrays (no copy): the commit and the Subscribe replies then read
+        what apply wrote."""
+        pt = PubTable(slot_of_id, slot_client_off, client, n_clients, None, [0],
+                      device=self.device)
+        (pt.cur_tag, pt.cur_fixed, pt.cur_aux, pt.cur_heap, pt.cur_ctag, pt.cur_cfixed,
+         pt.cur_caux) = self.as_pub_columns()
+        return pt
+
+    def as_columns(self, ids):
+        """An NxgColumns over the table's rows and children with `ids` (an int64 device tensor of
+        n_slots Ids) as the id column: input of nxg_encode_updates, its heap being t["heap"]."""
+        v = _ColumnsView()
+        v.device = self.device
+        v.t = dict(self.t, id=ids)
+        v.s = NxgColumns()
+        v.s.layout = LAYOUT_F64 if self.f64 else LAYOUT_MIXED
+        v.s.mem = MEM_DEVICE
+        v.s.cap_rows = v.s.n_rows = self.n_slots
+        v.s.cap_children = v.s.n_children = self.child_used
+        for name in ("id", "tag", "fixed", "aux", "ctag", "cfixed", "caux"):
+            setattr(v.s, name, _ptr(v.t.get(name)).value)
+        return v
+
+    def numpy(self):
+        """Host copies: the seven arrays (the written part of heap and children) and counters."""
+        import torch
+        torch.cuda.synchronize(self.device)
+        n, hu, ku = self.n_slots, self.heap_used, self.child_used
+        cut = {"slots": n, "bytes": hu, "children": ku}
+        out = {}
+        for name, dt, kind in self.ARRAYS:
+            t = self.t[name]
+            out[name] = None if t is None else t[:cut[kind]].cpu().numpy().view(
+                {"uint8": np.uint8, "int64": np.uint64, "int32": np.uint32}[dt])
+        return out
 
 
 NOT_SUBSCRIBED = 0xFFFFFFFF

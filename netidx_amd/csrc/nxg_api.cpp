@@ -2810,6 +2810,378 @@ bool nxg_encode_clients(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
     return pass(out->out, out->cap_bytes) && frames_ok();
 }
 
+// ---- the value table: `pbl.current = v` and a subscription's `last`, on the device --------------
+// (nxg_value_table.hip). Every call: argument checks on the host, the launches, one read-back of
+// the call's head, then the table's counters.
+namespace {
+const char* vt_cause(uint32_t cause) {
+    switch (cause & ~kVtOld) {
+    case kVtRow: return "src_row names a row at or past the batch's n_rows";
+    case kVtTag: return "a tag outside 0..27 and NXG_TAG_UNSUBSCRIBED";
+    case kVtHeap: return "a payload outside the heap";
+    case kVtKids: return "a child range outside the child columns";
+    case kVtNoKids: return "a container without child columns";
+    case kVtDepth: return "a value nested deeper than NXG_MAX_DEPTH";
+    case kVtNotF64: return "NXG_NOT_F64: a value that is not F64 for a table without a tag column";
+    case kVtSlot: return "a slot at or past n_slots";
+    default: return "unknown cause";
+    }
+}
+
+bool vt_refused(const NxgVtHead& h, NetidxError* err) {
+    if (!h.err_inv) return false;
+    const uint32_t cause = (uint32_t)(h.err_inv & 0xff);
+    const uint64_t slot = ~(h.err_inv >> 8 | 0xffull << 56);
+    set_err(err, "slot %llu: %s%s", (unsigned long long)slot, vt_cause(cause),
+            (cause & kVtOld) ? " (the value the table holds)" : "");
+    return true;
+}
+
+bool vt_table_ok(const NxgValueTable* t, const char* name, NetidxError* err) {
+    const bool mixed = t->tag != nullptr;
+    if (t->n_slots >= 0xffffffffull) {
+        set_err(err, "%s: a table holds fewer than 2^32 - 1 slots", name);
+        return false;
+    }
+    if ((t->n_slots && !t->fixed) || (mixed && !t->aux) ||
+        (mixed && t->cap_bytes && !t->heap) ||
+        (mixed && t->cap_children && (!t->ctag || !t->cfixed || !t->caux))) {
+        set_err(err, "%s: null array", name);
+        return false;
+    }
+    if (mixed && (t->heap_used > t->cap_bytes || t->child_used > t->cap_children ||
+                  t->heap_live > t->heap_used || t->child_live > t->child_used)) {
+        set_err(err, "%s: counters past their capacities (heap %llu live / %llu used / %llu, "
+                     "children %llu / %llu / %llu)", name, (unsigned long long)t->heap_live,
+                (unsigned long long)t->heap_used, (unsigned long long)t->cap_bytes,
+                (unsigned long long)t->child_live, (unsigned long long)t->child_used,
+                (unsigned long long)t->cap_children);
+        return false;
+    }
+    const void* ptrs[] = {t->tag, t->fixed, t->aux, mixed ? t->heap : nullptr,
+                          mixed ? t->ctag : nullptr, mixed ? t->cfixed : nullptr,
+                          mixed ? t->caux : nullptr};
+    for (const void* p : ptrs)
+        if (p && !is_device_ptr(p)) {
+            set_err(err, "%s: an array is not device memory", name);
+            return false;
+        }
+    return true;
+}
+
+void vt_spans(const NxgValueTable* t, std::vector<Span>* v) {
+    const bool mixed = t->tag != nullptr;
+    const uint64_t n = t->n_slots, k = mixed ? t->cap_children : 0;
+    const std::pair<const void*, uint64_t> a[] = {
+        {t->tag, n},       {t->fixed, n * 8},  {t->aux, mixed ? n * 4 : 0},
+        {t->heap, mixed ? t->cap_bytes : 0},   {t->ctag, k},
+        {t->cfixed, k * 8}, {t->caux, k * 4}};
+    for (const auto& x : a)
+        if (x.first && x.second) v->push_back(span_of(x.first, x.second));
+}
+
+NxgVtDst vt_dst(const NxgValueTable* t, bool fresh) {
+    const bool mixed = t->tag != nullptr;
+    NxgVtDst d{};
+    d.tag = t->tag;
+    d.fixed = t->fixed;
+    d.aux = mixed ? t->aux : nullptr;
+    d.n_slots = t->n_slots;
+    if (mixed) {
+        d.heap = t->heap;
+        d.ctag = t->ctag;
+        d.cfixed = t->cfixed;
+        d.caux = t->caux;
+        d.cap_bytes = t->cap_bytes;
+        d.cap_children = t->cap_children;
+        d.heap_used = fresh ? 0 : t->heap_used;
+        d.child_used = fresh ? 0 : t->child_used;
+    }
+    return d;
+}
+
+// the table as a source of values: what it has written so far bounds every range
+NxgVtSrc vt_src_of_table(const NxgValueTable* t) {
+    const bool mixed = t->tag != nullptr;
+    NxgVtSrc s{};
+    s.tag = t->tag;
+    s.fixed = t->fixed;
+    s.aux = mixed ? t->aux : nullptr;
+    s.n_rows = t->n_slots;
+    if (mixed) {
+        s.heap = t->heap;
+        s.heap_len = t->heap_used;
+        if (t->child_used) {
+            s.ctag = t->ctag;
+            s.cfixed = t->cfixed;
+            s.caux = t->caux;
+            s.n_children = t->child_used;
+        }
+    }
+    return s;
+}
+
+bool vt_batch(const NxgColumns* b, const uint8_t* heap, uint64_t heap_len, const uint64_t* src_row,
+              uint64_t n_sel, NxgVtSrc* out, std::vector<Span>* spans, NetidxError* err) {
+    NxgVtSrc s{};
+    if (b) {
+        const bool f64 = b->layout == NXG_LAYOUT_F64;
+        if (b->mem != NXG_MEM_DEVICE) {
+            set_err(err, "batch->mem: the value table takes device columns");
+            return false;
+        }
+        if (b->n_rows && (!b->fixed || (!f64 && (!b->tag || !b->aux)))) {
+            set_err(err, "batch: null column");
+            return false;
+        }
+        if (!f64 && b->n_children && (!b->ctag || !b->cfixed || !b->caux)) {
+            set_err(err, "batch: n_children without child columns");
+            return false;
+        }
+        s.tag = f64 ? nullptr : b->tag;
+        s.fixed = b->fixed;
+        s.aux = f64 ? nullptr : b->aux;
+        s.n_rows = b->n_rows;
+        if (!f64 && b->n_children) {
+            s.ctag = b->ctag;
+            s.cfixed = b->cfixed;
+            s.caux = b->caux;
+            s.n_children = b->n_children;
+        }
+        cols_spans(b, spans);
+    }
+    if (heap_len && !heap) {
+        set_err(err, "heap: null with heap_len %llu", (unsigned long long)heap_len);
+        return false;
+    }
+    s.heap = heap;
+    s.heap_len = heap ? heap_len : 0;
+    const void* ptrs[] = {s.tag, s.fixed, s.aux, s.ctag, s.cfixed, s.caux, s.heap, src_row};
+    for (const void* p : ptrs)
+        if (p && !is_device_ptr(p)) {
+            set_err(err, "batch, heap or src_row: not device memory");
+            return false;
+        }
+    if (s.heap && s.heap_len) spans->push_back(span_of(s.heap, s.heap_len));
+    if (src_row && n_sel) spans->push_back(span_of(src_row, n_sel * 8));
+    *out = s;
+    return true;
+}
+
+// the launches and the read-back; a segment list that turns out too short (rows named by many
+// slots) repeats the call once with the size just learned -- nothing was written
+bool vt_run(NxgCtx* c, NxgVtArgs a, uint64_t seg_cap, NxgVtHead* h, NetidxError* err) {
+    for (int attempt = 0;; attempt++) {
+        const size_t need = nxg_vt_scratch_bytes(a.dst.n_slots, seg_cap,
+                                                 a.dst.tag ? kVtPathMixed : kVtPathF64);
+        if (need > c->dscratch_cap) {
+            HIPCHK(hipStreamSynchronize(c->stream));
+            if (c->dscratch) HIPCHK(hipFree(c->dscratch));
+            c->dscratch = nullptr;
+            const size_t sz = std::max(need, c->dscratch_cap * 2);
+            c->dscratch_cap = 0;
+            HIPCHK(hipMalloc(&c->dscratch, sz));
+            c->dscratch_cap = sz;
+        }
+        a.seg_cap = seg_cap;
+        HIPCHK(nxg_launch_vt_apply(a, c->dscratch, c->ncu, c->stream));
+        HIPCHK(hipMemcpyAsync(h, c->dscratch, sizeof *h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        const bool fits = h->need_bytes <= a.dst.cap_bytes - a.dst.heap_used &&
+                          h->need_children <= a.dst.cap_children - a.dst.child_used;
+        if (!h->seg_short || h->err_inv || !fits || attempt) return true;
+        seg_cap = h->n_leaves;
+    }
+}
+
+bool vt_entry(NxgCtx* c, NetidxError* err) {
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    return set_device(c, err);
+}
+}  // namespace
+
+bool nxg_value_table_init(NxgCtx* c, NxgValueTable* t, NetidxError* err) {
+    if (!c || !t) {
+        set_err(err, "null argument");
+        return false;
+    }
+    {
+        NxgValueTable z = *t;  // the counters are outputs: reset only once nothing can refuse
+        z.heap_used = z.heap_live = z.child_used = z.child_live = 0;
+        if (!vt_table_ok(&z, "t", err) || !vt_entry(c, err)) return false;
+    }
+    if (t->n_slots) {
+        if (t->tag) {
+            HIPCHK(hipMemsetAsync(t->tag, 16, t->n_slots, c->stream));  // Value::Null
+            HIPCHK(hipMemsetAsync(t->aux, 0, t->n_slots * 4, c->stream));
+        }
+        HIPCHK(hipMemsetAsync(t->fixed, 0, t->n_slots * 8, c->stream));
+    }
+    HIPCHK(hipStreamSynchronize(c->stream));
+    t->heap_used = t->heap_live = t->child_used = t->child_live = 0;
+    return true;
+}
+
+bool nxg_value_table_apply(NxgCtx* c, NxgValueTable* t, const NxgColumns* batch,
+                           const uint8_t* heap, uint64_t heap_len, const uint64_t* src_row,
+                           NxgValueApply* out, NetidxError* err) {
+    if (!c || !t || !batch || !out || (t->n_slots && !src_row)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    *out = NxgValueApply{};
+    if (!vt_table_ok(t, "t", err)) return false;
+    NxgVtArgs a{};
+    std::vector<Span> tb, in;
+    if (!vt_batch(batch, heap, heap_len, src_row, t->n_slots, &a.batch, &in, err)) return false;
+    vt_spans(t, &tb);
+    if (overlaps(tb, in)) {
+        set_err(err, "the batch, its heap or src_row overlaps the table's arrays");
+        return false;
+    }
+    if (!vt_entry(c, err)) return false;
+    if (!t->n_slots) return true;
+    a.old = vt_src_of_table(t);
+    a.dst = vt_dst(t, false);
+    a.src_row = src_row;
+    a.n_sel = t->n_slots;
+    NxgVtHead h{};
+    const uint64_t seg = std::min(batch->n_rows + a.batch.n_children,
+                                  a.dst.cap_bytes - a.dst.heap_used);
+    if (!vt_run(c, a, seg, &h, err)) return false;
+    if (vt_refused(h, err)) return false;
+    out->n_applied = h.n_applied;
+    if (!t->tag) return true;  // an F64 table: no payload
+    out->need_bytes = h.need_bytes;
+    out->need_children = h.need_children;
+    out->live_bytes = t->heap_live - std::min(t->heap_live, h.old_bytes) + h.need_bytes;
+    out->live_children = t->child_live - std::min(t->child_live, h.old_children) + h.need_children;
+    if (!h.ok) {
+        set_err(err, "NXG_CAPACITY: the new values need %llu heap bytes and %llu child slots, the "
+                     "table has %llu and %llu left; it would hold %llu live bytes and %llu live "
+                     "child slots (nxg_value_table_rebuild)",
+                (unsigned long long)h.need_bytes, (unsigned long long)h.need_children,
+                (unsigned long long)(t->cap_bytes - t->heap_used),
+                (unsigned long long)(t->cap_children - t->child_used),
+                (unsigned long long)out->live_bytes, (unsigned long long)out->live_children);
+        return false;
+    }
+    t->heap_used += h.need_bytes;
+    t->child_used += h.need_children;
+    t->heap_live = out->live_bytes;
+    t->child_live = out->live_children;
+    return true;
+}
+
+bool nxg_value_table_rebuild(NxgCtx* c, const NxgValueTable* src, const NxgColumns* batch,
+                             const uint8_t* heap, uint64_t heap_len, const uint64_t* src_row,
+                             NxgValueTable* dst, NxgValueApply* out, NetidxError* err) {
+    if (!c || !src || !dst || !out) {
+        set_err(err, "null argument");
+        return false;
+    }
+    *out = NxgValueApply{};
+    if (!vt_table_ok(src, "src", err)) return false;
+    {
+        NxgValueTable d = *dst;  // dst's counters are outputs
+        d.heap_used = d.heap_live = d.child_used = d.child_live = 0;
+        if (!vt_table_ok(&d, "dst", err)) return false;
+    }
+    if (dst->n_slots < src->n_slots || (dst->tag == nullptr) != (src->tag == nullptr)) {
+        set_err(err, "dst: it needs at least src's %llu slots and src's kind (with or without a "
+                     "tag column)", (unsigned long long)src->n_slots);
+        return false;
+    }
+    if (!batch) src_row = nullptr;
+    NxgVtArgs a{};
+    std::vector<Span> db, in;
+    if (!vt_batch(batch, heap, heap_len, src_row, src->n_slots, &a.batch, &in, err)) return false;
+    vt_spans(src, &in);
+    vt_spans(dst, &db);
+    if (overlaps(db, in)) {
+        set_err(err, "dst overlaps src, the batch, its heap or src_row");
+        return false;
+    }
+    if (!vt_entry(c, err)) return false;
+    if (!dst->n_slots) {
+        dst->heap_used = dst->heap_live = dst->child_used = dst->child_live = 0;
+        return true;
+    }
+    a.old = vt_src_of_table(src);
+    a.dst = vt_dst(dst, true);
+    a.src_row = src_row;
+    a.n_sel = src->n_slots;
+    a.rebuild = 1;
+    NxgVtHead h{};
+    const uint64_t seg = std::min(a.batch.n_rows + a.batch.n_children + src->n_slots +
+                                      a.old.n_children, a.dst.cap_bytes);
+    if (!vt_run(c, a, seg, &h, err)) return false;
+    if (vt_refused(h, err)) return false;
+    out->n_applied = h.n_applied;
+    if (!dst->tag) return true;
+    out->need_bytes = out->live_bytes = h.need_bytes;
+    out->need_children = out->live_children = h.need_children;
+    if (!h.ok) {
+        set_err(err, "NXG_CAPACITY: the table's values need %llu heap bytes and %llu child slots, "
+                     "dst holds %llu and %llu",
+                (unsigned long long)h.need_bytes, (unsigned long long)h.need_children,
+                (unsigned long long)dst->cap_bytes, (unsigned long long)dst->cap_children);
+        return false;
+    }
+    dst->heap_used = dst->heap_live = h.need_bytes;
+    dst->child_used = dst->child_live = h.need_children;
+    return true;
+}
+
+bool nxg_value_table_set_unsubscribed(NxgCtx* c, NxgValueTable* t, const uint32_t* slot,
+                                      uint64_t n, NetidxError* err) {
+    if (!c || !t || (n && !slot)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (!vt_table_ok(t, "t", err)) return false;
+    if (!t->tag) {
+        set_err(err, "t: a table without a tag column cannot hold Event::Unsubscribed");
+        return false;
+    }
+    if (n >= 0xffffffffull || (n && !is_device_ptr(slot))) {
+        set_err(err, "slot: device memory, fewer than 2^32 - 1 entries");
+        return false;
+    }
+    std::vector<Span> tb;
+    vt_spans(t, &tb);
+    if (n && overlaps(tb, {span_of(slot, n * 4)})) {
+        set_err(err, "slot overlaps the table's arrays");
+        return false;
+    }
+    if (!vt_entry(c, err)) return false;
+    if (!n) return true;
+    NxgVtArgs a{};
+    a.old = vt_src_of_table(t);
+    a.dst = vt_dst(t, false);
+    const size_t need = nxg_vt_scratch_bytes(t->n_slots, 0, kVtPathUnsub);
+    if (need > c->dscratch_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
+        c->dscratch = nullptr;
+        const size_t sz = std::max(need, c->dscratch_cap * 2);
+        c->dscratch_cap = 0;
+        HIPCHK(hipMalloc(&c->dscratch, sz));
+        c->dscratch_cap = sz;
+    }
+    HIPCHK(nxg_launch_vt_unsub(a, slot, n, c->dscratch, c->stream));
+    NxgVtHead h{};
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (vt_refused(h, err)) return false;
+    t->heap_live -= std::min(t->heap_live, h.old_bytes);
+    t->child_live -= std::min(t->child_live, h.old_children);
+    return true;
+}
+
 bool nxg_encoded_len(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, uint64_t* len_out,
                      NetidxError* err) {
     return encode_impl(c, in, heap, nullptr, 0, len_out, err);

@@ -456,6 +456,79 @@ hipError_t nxg_launch_enc_clients(bool f64, const ColsDesc& cols, const uint8_t*
 int nxg_occupancy_enc_f64();
 int nxg_occupancy_enc_general();
 
+// the value table (nxg_value_table.hip): values folded into columns and storage the table owns.
+// A source of values: rows (tag null: all F64, aux null: 0), their children and their heap, each
+// with the bound the sizing pass checks against.
+struct NxgVtSrc {
+    const uint8_t* tag;
+    const uint64_t* fixed;
+    const uint32_t* aux;
+    const uint8_t* ctag;
+    const uint64_t* cfixed;
+    const uint32_t* caux;
+    const uint8_t* heap;
+    uint64_t n_rows, n_children, heap_len;
+};
+struct NxgVtDst {
+    uint8_t* tag;  // null: an F64 table
+    uint64_t* fixed;
+    uint32_t* aux;
+    uint8_t* heap;
+    uint8_t* ctag;
+    uint64_t* cfixed;
+    uint32_t* caux;
+    uint64_t n_slots, cap_bytes, cap_children;
+    uint64_t heap_used, child_used;  // the appends start here
+};
+// causes of a refused slot (the low byte of NxgVtHead.err_inv); kVtOld is added when the value
+// walked was the slot's old one
+enum : uint32_t {
+    kVtRow = 1, kVtTag = 2, kVtHeap = 3, kVtKids = 4, kVtNoKids = 5, kVtDepth = 6, kVtNotF64 = 7,
+    kVtSlot = 8, kVtOld = 16
+};
+struct NxgVtHead {  // device, zeroed per call, copied back whole after the last launch
+    uint64_t err_inv;  // ~slot << 8 | cause of the lowest refused slot (atomicMax; 0: none)
+    uint64_t n_applied;
+    uint64_t need_bytes, need_children, n_leaves;  // the new values' payload (the top kernel)
+    uint64_t old_bytes, old_children;              // the replaced values' payload
+    uint32_t ok;         // the top kernel: no refusal and everything fits; nothing is written before
+    uint32_t seg_short;  // more heap-borne leaves than the segment list holds
+    uint64_t pad[8];
+};
+static_assert(sizeof(NxgVtHead) == 128, "NxgVtHead layout");
+struct NxgVtArgs {
+    NxgVtSrc batch;  // the values of the selected slots: row src_row[s] - 1
+    NxgVtSrc old;    // apply: the table itself (old values are sized); rebuild: the source table
+    NxgVtDst dst;
+    const uint64_t* src_row;  // [n_sel] 1 + row, 0: not selected; null: none selected
+    uint64_t n_sel;           // apply: n_slots; rebuild: the source table's slots
+    uint32_t rebuild;         // unselected slots take old's value (past n_sel: Null)
+    // scratch, placed by the launcher
+    NxgVtHead* head;
+    uint64_t* lbytes;   // per slot: new heap bytes / child slots / leaves before it in its block
+    uint64_t* lkids;
+    uint64_t* lleaves;
+    uint64_t* bbytes;   // per block of kVtBlock slots: the sums, then (top kernel) the bases
+    uint64_t* bkids;
+    uint64_t* bleaves;
+    uint64_t* bold;     // per block, three arrays of n blocks: replaced bytes, replaced child slots,
+                        // selected slots (summed by the top kernel: no atomics on one word)
+    uint64_t* seg_dst;  // [seg_cap + 1] per heap-borne leaf: where its bytes go in dst.heap ...
+    uint64_t* seg_src;  // [seg_cap] ... and where they are (an address)
+    uint64_t seg_cap;
+    uint32_t* bitmap;   // set_unsubscribed: one bit per slot (zeroed)
+};
+constexpr int kVtBlock = 256;
+// `scratch` holds nxg_vt_scratch_bytes(dst.n_slots, seg_cap, path) bytes, `path` being the one the
+// launcher takes (apply: mixed or F64 by dst.tag; unsub); only the head (at its start) is
+// initialised, by the launchers. a.head is at `scratch` afterwards.
+enum { kVtPathMixed = 0, kVtPathF64 = 1, kVtPathUnsub = 2 };
+uint64_t nxg_vt_scratch_bytes(uint64_t n_slots, uint64_t seg_cap, int path);
+hipError_t nxg_launch_vt_apply(NxgVtArgs a, uint8_t* scratch, int ncu, hipStream_t s);
+// the named slots' old values sized (each slot once) and replaced by NXG_TAG_UNSUBSCRIBED
+hipError_t nxg_launch_vt_unsub(NxgVtArgs a, const uint32_t* slot, uint64_t n, uint8_t* scratch,
+                               hipStream_t s);
+
 // Device-side copy of the column pointers (passed by value to kernels).
 struct ColsDesc {
     uint64_t cap_rows, cap_children, cap_ctl;
