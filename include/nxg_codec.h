@@ -1071,6 +1071,62 @@ bool nxg_decode_archive_batch(NxgCtx* ctx, const uint8_t* buf, uint64_t len, Nxg
 bool nxg_encode_archive_batch(NxgCtx* ctx, const NxgColumns* in, const uint8_t* heap,
                               uint8_t* out, uint64_t cap, uint64_t* len_out, NetidxError* err);
 
+/* ---- recording: replaces the recorder's batch loop (netidx-archive/src/recorder/record.rs:
+ * 307-347): every (SubId, Event) of a channel's batch is translated through by_subid to the
+ * archive's Id, entries without one are dropped, and the rest become one archive batch
+ * (<Vec<BatchItem> as Pack>::encode, writer.rs:399-428). Here a dispatch's entry list becomes the
+ * records of all its channels in one call.
+ * `batch` and `heap` are what the dispatch was made from: device columns of either layout (for a
+ * decoded frame the heap is the frame); control spans in `batch` are ignored. `d` is the result of
+ * nxg_dispatch_updates or nxg_route_replies (disp), or any entry list of that form; d->last_row is
+ * not read. Per channel c, over its entries e in [d->chan_off[c], d->chan_off[c+1]), in order:
+ *   sub = d->ent_sub[e]; the entry is kept iff sub < tab->n_subs and arch_id_of_sub[sub] !=
+ *   NXG_NO_SLOT. Any other entry is dropped and counted in n_dropped, and nothing else of it is
+ *   read (its ent_row may be anything).
+ *   A kept entry becomes the item varint(arch_id) Event: the byte 0x40 when ent_row[e] has
+ *   NXG_ENT_SPAN set (the span index is not read) or when the row's tag is NXG_TAG_UNSUBSCRIBED,
+ *   else the bare Value of batch row ent_row[e] as nxg_encode_archive_batch writes it (a row of
+ *   F64-layout columns: 09 and the 8 bytes big-endian).
+ *   The record is varint(rec_items[c]) and the items: byte for byte what nxg_encode_archive_batch
+ *   writes for the kept entries' rows gathered into columns with id = arch_id. A channel without a
+ *   kept entry gets no bytes (add_batch writes nothing for an empty batch, writer.rs:405):
+ *   rec_off[c] == rec_off[c+1], rec_items[c] == 0.
+ * Records lie back to back in channel order: rec_off[0] == 0, rec_off[n_chans] == n_bytes. Entries
+ * may name rows in any order and any number of times, and rows may share children. Entries in front
+ * of chan_off[0] belong to no channel: they are neither read, kept nor counted.
+ * false with a message:
+ *   on misuse, before any launch (a null argument, host memory, d->n_entries > d->cap_entries,
+ *     2^39 entries or more, async work pending on the ctx);
+ *   when chan_off[0 .. n_chans] decreases or does not end at d->n_entries (found on the device;
+ *     the message names the lowest channel c with chan_off[c+1] < chan_off[c], or the last channel
+ *     when only the end differs);
+ *   for a kept entry with ent_row >= batch->n_rows, or whose row has an unknown tag, violates a
+ *     size guard (PackError::TooBig), has a child range outside n_children, is a container with
+ *     elements but no child columns, or nests past NXG_MAX_DEPTH: the message names the lowest such
+ *     entry and its cause, whatever the scheduling;
+ *   when rec_items[c] * size_of::<BatchItem>() exceeds MAX_VEC (TooBig; the first such channel);
+ *   when n_bytes > cap_bytes: n_bytes, n_items, n_dropped, rec_off and rec_items then hold the
+ *     true values.
+ * Every check and every size is settled before the first byte of `out` is written: after any false
+ * return no byte of `out` has changed. Whatever the outcome, nothing outside [out, out +
+ * cap_bytes), rec_off[0 .. n_chans] and rec_items[0 .. n_chans) is written. d->n_entries == 0
+ * gives all zeros. Synchronous, one read-back of a small head; out NULL sizes only (the same
+ * read-back, no writing kernel). */
+typedef struct NxgRecordTable {      /* by_subid: FxHashMap<SubId, Id>, record.rs:196 */
+    uint64_t n_subs;                 /* arch_id_of_sub covers SubIds [0, n_subs) (SubIds come from a counter) */
+    const uint32_t* arch_id_of_sub;  /* device; the archive Id, or NXG_NO_SLOT: by_subid has no entry */
+} NxgRecordTable;
+typedef struct NxgRecordBatches {
+    uint64_t cap_bytes;   /* capacity of out */
+    uint8_t* out;         /* device; NULL: size only */
+    uint64_t* rec_off;    /* device [n_chans + 1]: channel c's record is out[rec_off[c], rec_off[c+1]) */
+    uint64_t* rec_items;  /* device [n_chans]: items in channel c's record */
+    uint64_t n_bytes, n_items, n_dropped;   /* written by the call */
+} NxgRecordBatches;
+bool nxg_record_entries(NxgCtx* ctx, const NxgColumns* batch, const uint8_t* heap,
+                        const NxgDispatch* d, uint32_t n_chans, const NxgRecordTable* tab,
+                        NxgRecordBatches* out, NetidxError* err);
+
 /* ---- compressed archive batches: replaces the compressed branch of ArchiveReader::get_batch_at
  * (netidx-archive/src/logfile/reader.rs:453-477): a record after its RecordHeader is
  * u32 BE uncompressed record length | the RecordIndex (indexed files: a varint that is its own

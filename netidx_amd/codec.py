@@ -112,6 +112,16 @@ class NxgClientFrames(C.Structure):
                 ("n_bytes", C.c_uint64)]
 
 
+class NxgRecordTable(C.Structure):
+    _fields_ = [("n_subs", C.c_uint64), ("arch_id_of_sub", C.c_void_p)]
+
+
+class NxgRecordBatches(C.Structure):
+    _fields_ = [("cap_bytes", C.c_uint64), ("out", C.c_void_p), ("rec_off", C.c_void_p),
+                ("rec_items", C.c_void_p), ("n_bytes", C.c_uint64), ("n_items", C.c_uint64),
+                ("n_dropped", C.c_uint64)]
+
+
 class NxgWriteTable(C.Structure):
     _fields_ = [("n_ids", C.c_uint64), ("perm_of_id", C.c_void_p), ("slot_of_id", C.c_void_p),
                 ("n_slots", C.c_uint64), ("slot_chan_off", C.c_void_p), ("chan", C.c_void_p),
@@ -357,6 +367,10 @@ SIGNATURES = {
                                       C.POINTER(NetidxError)]),
     "nxg_publish_unsubscribes": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                             C.c_uint32, C.c_void_p, C.POINTER(NetidxError)]),
+    "nxg_record_entries": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
+                                      C.POINTER(NxgDispatch), C.c_uint32,
+                                      C.POINTER(NxgRecordTable), C.POINTER(NxgRecordBatches),
+                                      C.POINTER(NetidxError)]),
     "nxg_encode_clients": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
                                       C.POINTER(NxgDispatch), C.c_uint32,
                                       C.POINTER(NxgClientFrames), C.POINTER(NetidxError)]),
@@ -1034,6 +1048,61 @@ class Codec:
             cap = out.numel()
         n, off = self.encode_clients_into(batch, dispatch, heap, out.data_ptr(), cap, off)
         return out[:n], off
+
+    def record_entries_into(self, batch, dispatch, table, heap, out_ptr, cap, rec_off=None,
+                            rec_items=None):
+        """nxg_record_entries into device memory at `out_ptr` (0 / None: size only). `dispatch`: a
+        Dispatch (dispatch_updates', route_replies' disp, or any chan_off / ent_sub / ent_row
+        device tensors with n_entries); `table`: arch_id_of_sub, a uint32 (int32 storage) device
+        tensor. Returns (n_bytes, rec_off, rec_items, n_items, n_dropped); a CodecError raised here
+        carries n_bytes, rec_off and rec_items."""
+        import torch
+        n_chans = dispatch.chan_off.numel() - 1
+        dev = dispatch.chan_off.device
+        if rec_off is None:
+            rec_off = torch.empty(n_chans + 1, dtype=torch.int64, device=dev)
+        if rec_items is None:
+            rec_items = torch.empty(max(n_chans, 1), dtype=torch.int64, device=dev)
+        d = NxgDispatch(dispatch.ent_row.numel(), dispatch.chan_off.data_ptr(),
+                        dispatch.ent_sub.data_ptr(), dispatch.ent_row.data_ptr(), None,
+                        int(dispatch.n_entries), 0)
+        t = NxgRecordTable(table.numel(), table.data_ptr() if table.numel() else None)
+        o = NxgRecordBatches(cap, out_ptr or None, rec_off.data_ptr(), rec_items.data_ptr(),
+                             0, 0, 0)
+        err = NetidxError()
+        try:
+            _check(lib().nxg_record_entries(self.ctx, C.byref(batch.s), _heap_ptr(heap),
+                                            C.byref(d), n_chans, C.byref(t), C.byref(o),
+                                            C.byref(err)), err)
+        except CodecError as e:
+            e.n_bytes, e.rec_off, e.rec_items = int(o.n_bytes), rec_off, rec_items
+            raise
+        return int(o.n_bytes), rec_off, rec_items[:n_chans], int(o.n_items), int(o.n_dropped)
+
+    def recorded_len(self, batch, dispatch, table, heap=None):
+        """The size-only form of record_entries: (n_bytes, rec_off, rec_items, n_dropped), nothing
+        encoded."""
+        n, off, items, _, dropped = self.record_entries_into(batch, dispatch, table, heap, None, 0)
+        return n, off, items, dropped
+
+    def record_entries(self, batch, dispatch, table, heap=None, out=None):
+        """A dispatch's entries as archive batch records in one call (the recorder's batch loop,
+        record.rs:307-347): `batch` and `heap` are what the dispatch was made from, `table`
+        arch_id_of_sub (SubId -> archive Id, NO_SLOT: not recorded). Returns (bytes, rec_off,
+        rec_items, n_dropped): channel c's record is bytes[rec_off[c]:rec_off[c+1]], rec_items[c]
+        items (uint8 / int64 tensors on the dispatch's device). `out`: a uint8 device tensor to
+        encode into (all of it is the capacity); without one the call sizes first and allocates."""
+        import torch
+        off = items = None
+        if out is None:
+            n, off, items, _ = self.recorded_len(batch, dispatch, table, heap)
+            out = torch.empty(max(n, 16), dtype=torch.uint8, device=dispatch.chan_off.device)
+            cap = n
+        else:
+            cap = out.numel()
+        n, off, items, _, dropped = self.record_entries_into(batch, dispatch, table, heap,
+                                                             out.data_ptr(), cap, off, items)
+        return out[:n], off, items, dropped
 
     def encoded_len(self, cols, heap=None):
         n, err = C.c_uint64(0), NetidxError()

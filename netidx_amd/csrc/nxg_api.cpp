@@ -17,6 +17,7 @@
 #include "../../include/nxg_codec.h"
 #include "nxg_internal.h"
 #include "nxg_path_hash.h"
+#include "nxg_record.h"
 
 namespace {
 
@@ -2808,6 +2809,140 @@ bool nxg_encode_clients(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
         }
     }
     return pass(out->out, out->cap_bytes) && frames_ok();
+}
+
+// ---- a dispatch's entries as archive batch records (the recorder's batch loop, record.rs:307-347)
+// (nxg_record.hip). Argument checks on the host, the launches, one read-back of the call's head.
+namespace {
+const char* rec_cause(uint32_t cause) {
+    switch (cause) {
+    case kRecRow: return "ent_row names a row at or past the batch's n_rows";
+    case kRecTag: return "an unknown tag (PackError kind 1)";
+    case kRecBig: return "a size guard (PackError::TooBig)";
+    case kRecKids: return "a child range outside the batch's n_children";
+    case kRecNoKids: return "a container with elements but no child columns";
+    case kRecDepth: return "a value nested deeper than NXG_MAX_DEPTH";
+    default: return "unknown cause";
+    }
+}
+}  // namespace
+
+bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
+                        const NxgDispatch* d, uint32_t n_chans, const NxgRecordTable* tab,
+                        NxgRecordBatches* out, NetidxError* err) {
+    if (!c || !batch || !d || !tab || !out || !d->chan_off || !out->rec_off ||
+        (n_chans && !out->rec_items) || (tab->n_subs && !tab->arch_id_of_sub)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    const uint64_t ne = d->n_entries;
+    const bool f64 = batch->layout == NXG_LAYOUT_F64;
+    if (ne && (!d->ent_sub || !d->ent_row)) {
+        set_err(err, "null entry array");
+        return false;
+    }
+    if (batch->n_rows && (!batch->fixed || (!f64 && (!batch->tag || !batch->aux)))) {
+        set_err(err, "null batch column");
+        return false;
+    }
+    if (ne > d->cap_entries) {
+        set_err(err, "d->n_entries (%llu) exceeds d->cap_entries (%llu)", (unsigned long long)ne,
+                (unsigned long long)d->cap_entries);
+        return false;
+    }
+    if (ne >= (1ull << 39)) {
+        set_err(err, "too many entries for one call (%llu)", (unsigned long long)ne);
+        return false;
+    }
+    const bool kids = !f64 && batch->n_children && batch->ctag && batch->cfixed && batch->caux;
+    {
+        const void* need[] = {d->chan_off, out->rec_off, n_chans ? out->rec_items : nullptr,
+                              out->out, heap, tab->n_subs ? tab->arch_id_of_sub : nullptr,
+                              ne ? d->ent_sub : nullptr, ne ? d->ent_row : nullptr,
+                              batch->n_rows ? batch->fixed : nullptr,
+                              batch->n_rows && !f64 ? batch->tag : nullptr,
+                              batch->n_rows && !f64 ? batch->aux : nullptr,
+                              kids ? batch->ctag : nullptr, kids ? batch->cfixed : nullptr,
+                              kids ? batch->caux : nullptr};
+        bool dev = batch->mem == NXG_MEM_DEVICE;
+        for (const void* p : need) dev = dev && (!p || is_device_ptr(p));
+        if (!dev) {
+            set_err(err, "nxg_record_entries takes device memory only (batch, heap, the dispatch's "
+                         "arrays, tab->arch_id_of_sub, out->out, out->rec_off and out->rec_items)");
+            return false;
+        }
+    }
+    if (!c->pending.empty()) {
+        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+        return false;
+    }
+    if (!set_device(c, err)) return false;
+    out->n_bytes = out->n_items = out->n_dropped = 0;
+    if (ne == 0) {  // no entries: no record, and no kernel runs
+        HIPCHK(hipMemsetAsync(out->rec_off, 0, ((uint64_t)n_chans + 1) * 8, c->stream));
+        if (n_chans) HIPCHK(hipMemsetAsync(out->rec_items, 0, (uint64_t)n_chans * 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    NxgRecArgs a{};
+    a.cols = desc_of(batch);
+    a.cols.n_ctl = 0;
+    if (f64) a.cols.tag = nullptr, a.cols.aux = nullptr;
+    if (!kids) {
+        a.cols.ctag = nullptr, a.cols.cfixed = nullptr, a.cols.caux = nullptr;
+        a.cols.n_children = 0;
+    }
+    a.heap = heap;
+    a.ent_sub = d->ent_sub;
+    a.ent_row = d->ent_row;
+    a.chan_off = d->chan_off;
+    a.n_ent = ne;
+    a.n_chans = n_chans;
+    a.arch_id_of_sub = tab->arch_id_of_sub;
+    a.n_subs = tab->n_subs;
+    a.out = out->out;
+    a.cap = out->out ? out->cap_bytes : 0;
+    a.rec_off = out->rec_off;
+    a.rec_items = out->rec_items;
+    const size_t need = nxg_rec_scratch_bytes(ne, n_chans);
+    if (need > c->dscratch_cap) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
+        c->dscratch = nullptr;
+        const size_t sz = std::max(need, c->dscratch_cap * 2);
+        c->dscratch_cap = 0;
+        HIPCHK(hipMalloc(&c->dscratch, sz));
+        c->dscratch_cap = sz;
+    }
+    NxgRecHead h;
+    HIPCHK(nxg_launch_record(a, c->dscratch, c->stream));
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.chan_bad) {
+        set_err(err, "d->chan_off is not a dispatch's at channel %u: it must not decrease and "
+                     "must end at d->n_entries (%llu)", h.chan_bad - 1, (unsigned long long)ne);
+        return false;
+    }
+    if (h.err_inv) {
+        const uint64_t entry = ~(h.err_inv >> 8 | 0xffull << 56);
+        set_err(err, "entry %llu: %s", (unsigned long long)entry,
+                rec_cause((uint32_t)(h.err_inv & 0xff)));
+        return false;
+    }
+    if (h.vec_bad) {
+        set_err(err, "encode failed: channel %u's items exceed MAX_VEC (PackError::TooBig)",
+                h.vec_bad - 1);
+        return false;
+    }
+    out->n_bytes = h.n_bytes;
+    out->n_items = h.n_items;
+    out->n_dropped = h.n_dropped;
+    if (out->out && h.n_bytes > out->cap_bytes) {
+        set_err(err, "output buffer too small: need %llu bytes, have %llu",
+                (unsigned long long)h.n_bytes, (unsigned long long)out->cap_bytes);
+        return false;
+    }
+    return true;
 }
 
 // ---- the value table: `pbl.current = v` and a subscription's `last`, on the device --------------
