@@ -884,6 +884,14 @@ class Codec:
         lib().nxg_debug_diag(C.c_void_p(self.ctx), a)
         return list(a)
 
+    def last_route(self):
+        """(decoder, seq_left, irregular_left, mix_left) (diagnostics, not ABI): the decoder that
+        produced the last completed decode -- 1 length-run, 2 single-pass, 3 fast mixed,
+        4 sequential-id, 0 general -- and the context's three countdowns."""
+        a = (C.c_uint * 4)()
+        lib().nxg_debug_route(C.c_void_p(self.ctx), a)
+        return tuple(a)
+
     def last_encode_kernel(self):
         """Which f64 encoder wrote the last f64 encode (diagnostics, not ABI): "seq" for the
         sequential-id kernel (nxg_encode_f64_seq.hip), "tile" for the tiled look-back kernel."""

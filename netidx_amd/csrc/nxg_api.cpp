@@ -110,6 +110,7 @@ struct NxgCtx {
     // (NXG_MIXED_PATH=general: always the general decoder)
     uint32_t mix_left = 0;
     bool no_fmx = false;
+    uint32_t last_route = 0;  // the decoder of the last finish_decode: a FAST_* code (debug)
     // the fast mixed decoder's count pass: lean (one-byte-prefix Update candidates only, then the
     // tiles where that found no chain recounted from every kind) while this connection's last
     // decoded frame had at most 1 tile in 32 holding a Heartbeat or a two-byte prefix
@@ -539,6 +540,7 @@ bool finish_decode(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* out, i
         const bool ok = enqueue_dec_x(c, f, len, out, st2, err);
         if (!end_call(c, err) || !ok) return false;
         if (redone) *redone = true;
+        tried_fast = FAST_X;
         HIPCHK(hipMemcpyAsync(c->hst + slot2, st2, sizeof(DevStatus), hipMemcpyDeviceToHost,
                               c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -566,6 +568,7 @@ bool finish_decode(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* out, i
         h = c->hst[slot2];
         tried_fast = next;
     }
+    c->last_route = (uint32_t)tried_fast;
     // the next fast mixed decode's count pass from this frame's mix of tiles
     if (h.path == 4 && len > 0) c->fmx_full = h.diag[0] * 32 > (len + 4095) / 4096;
     if (h.err_key) {  // general decode: the earliest (offset, kind) on the true chain
@@ -901,6 +904,15 @@ void nxg_debug_status(NxgCtx* c, unsigned long long out[6]) {
 }
 // Not part of the ABI: which f64 encoder wrote the last f64 encode (1 sequential-id, 2 tiled).
 unsigned nxg_debug_enc_kernel(NxgCtx* c) { return c ? c->last_enc_kernel : 0u; }
+// Not part of the ABI: the decoder that produced the last completed decode (the FAST_* code of
+// the final attempt: 1 length-run, 2 single-pass, 3 fast mixed, 4 sequential-id, 0 general) and
+// the connection's countdowns seq_left, irregular_left, mix_left.
+void nxg_debug_route(NxgCtx* c, unsigned out[4]) {
+    out[0] = c ? c->last_route : 0u;
+    out[1] = c ? c->seq_left : 0u;
+    out[2] = c ? c->irregular_left : 0u;
+    out[3] = c ? c->mix_left : 0u;
+}
 void nxg_debug_diag(NxgCtx* c, unsigned long long out[8]) {
     for (int i = 0; i < 8; i++) out[i] = c ? c->last.diag[i] : 0;
 }

@@ -254,7 +254,9 @@ NXG_DEV void subtile_starts(const uint8_t* __restrict__ wire, const XRange& rg, 
     } else if (q == ~0ull) {
         uint32_t x = FAILX;
         if (lane == 0) {
-            x = merge16i(im, 0, ib, W);
+            // (a range that begins fewer than 64 bytes into the frame: the walk starts at the
+            // frame's first byte, image offset XLO - pre; there are no 16 bytes at a0 - 64)
+            x = a0 == 0 && rg.pre < XLO ? XLO - (uint32_t)rg.pre : merge16i(im, 0, ib, W);
             while (x < XLO) {
                 uint32_t e0, e1, e2, e3;
                 lds16i(im, x, e0, e1, e2, e3);

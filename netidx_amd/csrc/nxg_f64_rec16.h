@@ -281,7 +281,13 @@ NXG_DEV void exact_tile(const uint8_t* __restrict__ wire, uint64_t W, uint64_t R
         // segment starts: lane 0 the chunk before a0, lane j >= 1 chunk j; ends: the next lane's
         // start, lane 63 the merge point of the chunk at a0 + 4096
         uint32_t xa;
-        if (lane == 0) xa = (a0 == 0 && first) ? kXLo : merge16(buf, 0, ib, W);
+        // (a range that begins fewer than 64 bytes into the frame sees the frame's first byte,
+        // a certain record start, at image offset kXLo - pre: the chunk before it holds no bytes
+        // to merge walks in)
+        if (lane == 0)
+            xa = (a0 == 0 && first)      ? kXLo
+                 : (a0 == 0 && pre < kXLo) ? kXLo - (uint32_t)pre
+                                           : merge16(buf, 0, ib, W);
         else xa = merge16(buf, kXLo + lane * 64, ib, W);
         uint32_t xb = wave_next(xa);
         if (lane == 63) xb = merge16(buf, kXHi, ib, W);

@@ -41,6 +41,7 @@ import numpy as np
 import pytest
 
 import decode_bounds_cases as dbc
+import f64_run_cases
 import nxo
 from guards import assert_guards, guarded_columns
 
@@ -51,7 +52,8 @@ ENV = {"seq": {}, "run": {"NXG_F64_PATH": "run", "NXG_F64R_FLAGS": "2"},
        "host": {}, "archive_fast": {}, "archive_exact": {"NXG_ARCH_PATH": "exact"}}
 MIXED_COLS = ("id", "tag", "fixed", "aux", "ctag", "cfixed", "caux", "ctl_row", "ctl_off",
               "ctl_len", "ctl_variant")
-MIX_FAIL_CALLS = 16  # calls for which a context skips the fast mixed decoder after it declined
+# calls for which a context skips the fast mixed decoder after it declined (nxg_api.cpp)
+MIX_FAIL_CALLS = f64_run_cases.constants()["kMixFailCalls"]
 
 
 @pytest.fixture(scope="module")
