@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nxg_codec.h"
+#include "nxg_devbuf.h"
 #include "nxg_internal.h"
 #include "nxg_path_hash.h"
 #include "nxg_record.h"
@@ -69,21 +70,18 @@ struct NxgCtx {
     // Every error return of a function that enqueues gathers clears the record (gather_forget).
     uint32_t gathered_to = 0;
     uint32_t epoch = 0;
-    uint64_t* tstat = nullptr;
-    size_t tstat_words = 0;
-    uint32_t* glws = nullptr;      // general decode: lane words, 256 B per tile
-    size_t glws_cap = 0;
+    // (every DevBuf frees itself with the ctx: a new one needs no line in nxg_ctx_destroy)
+    DevBuf<uint64_t> tstat;
+    DevBuf<uint8_t> glws;          // general decode: lane words, 256 B per tile
     uint64_t* gruns = nullptr;     // general decode: run summaries + bases
     bool no_fa = false;            // NXG_ARCH_PATH=exact: archive batches on the exact decoder only
-    uint8_t* dscratch = nullptr;   // dispatch: counters, offsets, block sums, unmatched count
-    size_t dscratch_cap = 0;
+    DevBuf<uint8_t> dscratch;      // dispatch: counters, offsets, block sums, unmatched count
     int wgs_dec_gen = 0;
     // f64 decoder choice: the length-run decoder (nxg_decode_f64_run.hip) unless the frames of
     // this connection have record lengths that vary record to record; then the single-pass
     // decoder of any f64 frame (nxg_decode_f64_x.hip) for the next kIrregularCalls calls
     // (NXG_F64_PATH=x forces it)
-    uint8_t* rdesc = nullptr;  // length-run decoder: 16-byte tile descriptors
-    size_t rdesc_cap = 0;
+    DevBuf<uint8_t> rdesc;  // length-run decoder: 16-byte tile descriptors
     uint32_t irregular_left = 0;
     bool force_x = false;
     // before both: the one-launch decoder of frames whose ids count up by one
@@ -100,8 +98,7 @@ struct NxgCtx {
     // the sequential-id f64 encoder (nxg_encode_f64_seq.hip): after it declines a batch (ids not
     // counting up by one) it is skipped for the next kSeqSkipCalls f64 encodes; NXG_F64_ENC=tile
     // skips it always
-    uint8_t* pscratch = nullptr;  // the type-partitioned view's counts and offsets
-    size_t pscratch_cap = 0;
+    DevBuf<uint8_t> pscratch;  // the type-partitioned view's counts and offsets
     uint32_t enc_seq_left = 0;
     uint32_t last_enc_kernel = 0;  // the last f64 encode: 1 sequential-id kernel, 2 tiled (debug)
     bool no_enc_seq = false;
@@ -121,28 +118,21 @@ struct NxgCtx {
     int wgs_fmx[2] = {0, 0};
     uint32_t f64r_flags = 0;  // NXG_F64R_FLAGS (tests): 1 every tile exact, 2 never hand over
     uint32_t patience = 128;  // NXG_LOOKBACK_PATIENCE: look-back polls before self-help
-    uint8_t* dframe = nullptr;
-    size_t dframe_cap = 0;
-    uint64_t* escratch = nullptr;
-    size_t escratch_words = 0;
+    DevBuf<uint8_t> dframe;
+    DevBuf<uint64_t> escratch;
     NxgColumns dcols{};  // device staging columns for host-resident outputs/inputs
     bool dcols_valid = false;
-    uint8_t* dheap = nullptr;
-    size_t dheap_cap = 0;
+    DevBuf<uint8_t> dheap;
     // device staging of a host-resident NxgWriteCols (nxg_decode_writes / nxg_encode_writes)
-    uint8_t* dwflags = nullptr;
-    uint64_t* dwid = nullptr;
-    size_t dw_cap = 0;
+    DevBuf<uint8_t> dwflags;
+    DevBuf<uint64_t> dwid;
     // write routing (nxg_route_writes.hip): the first Unsubscribe row per Id, tagged with the
     // call's epoch (24 bits; the table is cleared when it is grown and when the epoch wraps)
-    uint64_t* rw_first = nullptr;
-    size_t rw_first_cap = 0;
+    DevBuf<uint64_t> rw_first;
     uint32_t rw_epoch = 0;
     // reply routing (nxg_route_replies.hip): the first span per Id and per pending request, tagged
     // likewise with one epoch for both
-    uint64_t* rr_first_id = nullptr;
-    uint64_t* rr_first_q = nullptr;
-    size_t rr_first_id_cap = 0, rr_first_q_cap = 0;
+    DevBuf<uint64_t> rr_first_id, rr_first_q;
     uint32_t rr_epoch = 0;
     // in-flight async operations (completed in order by nxg_ctx_sync)
     struct Pending {
@@ -165,31 +155,22 @@ struct NxgCtx {
     void* zdefs = nullptr;
     uint8_t* zlit = nullptr;
     int zgrid = 0;
-    void* zrecs = nullptr;
-    size_t zrecs_cap = 0;
+    DevBuf<uint8_t> zrecs;
     // zstd compression (nxg_archive_compress): the predefined distributions' encoding tables, the
     // waves' literal / sequence slabs, descriptors, the frames' slots and their packed copy
     void* zc_tables = nullptr;
     uint8_t* zc_slab = nullptr;
     int zc_grid = 0;
-    uint8_t* zc_recs = nullptr;
-    size_t zc_recs_cap = 0;
-    uint8_t* zc_out = nullptr;
-    size_t zc_out_cap = 0;
-    uint8_t* zc_pack = nullptr;
-    size_t zc_pack_cap = 0;
-    uint8_t* zc_hpin = nullptr;  // pinned host staging of the packed frames
-    size_t zc_hpin_cap = 0;
+    DevBuf<uint8_t> zc_recs, zc_out, zc_pack;
+    DevBuf<uint8_t, DevMem::Pinned> zc_hpin;  // pinned host staging of the packed frames
     hipEvent_t zc_ev[2] = {nullptr, nullptr};  // around the compressor kernel (diagnostics)
     float zc_kernel_ms = 0.f;
     DevStatus last{};  // last completed decode's device status (diagnostics)
     uint64_t fa_last[8] = {};  // the last fast archive attempt's FaHead (diagnostics)
     // a window of archive records / its image (nxg_archive_window.hip): the head and the records
     // or the image's table, and the pinned host mirror of head + records
-    uint8_t* aw_dev = nullptr;
-    size_t aw_dev_cap = 0;
-    uint8_t* aw_host = nullptr;
-    size_t aw_host_cap = 0;
+    DevBuf<uint8_t> aw_dev;
+    DevBuf<uint8_t, DevMem::Pinned> aw_host;
     uint64_t last_split = 0;  // last completed encode's DevStatus.split_start
 };
 
@@ -213,7 +194,7 @@ bool begin_call(NxgCtx* c, DevStatus** st, uint32_t* slot, NetidxError* err) {
     c->epoch++;
     if (c->epoch > kEpochMax) {  // wrap: stale words could alias epoch 1 again
         c->epoch = 1;
-        if (c->tstat) HIPCHK(hipMemsetAsync(c->tstat, 0, c->tstat_words * 8, c->stream));
+        if (c->tstat) HIPCHK(hipMemsetAsync(c->tstat, 0, c->tstat.cap() * 8, c->stream));
     }
     return true;
 }
@@ -250,28 +231,48 @@ void gather_forget(NxgCtx* c) {
     c->gathered_to = c->pending.empty() ? c->calls : c->pending.front().seq;
 }
 
+// Grows `b` to hold `need` elements (nxg_devbuf.h: the steps, and what a failure leaves behind).
+template <class Buf, class Ops>
+bool grow_with(Buf& b, size_t need, GrowPolicy pol, Ops& ops, NetidxError* err) {
+    const GrowFail f = b.grow(need, pol, ops);
+    if (!f.step) return true;
+    set_err(err, "growing a buffer to %zu elements: %s failed: %s", need, f.step,
+            Ops::errstr(f.code));
+    return false;
+}
+
+template <class Buf>
+bool grow(NxgCtx* c, Buf& b, size_t need, GrowPolicy pol, NetidxError* err) {
+    HipOps ops{c->stream};
+    return grow_with(b, need, pol, ops, err);
+}
+
+// the scratch of whichever entry point runs (bytes)
+bool ensure_dscratch(NxgCtx* c, size_t need, NetidxError* err) {
+    return grow(c, c->dscratch, need, kGrowDouble, err);
+}
+
 bool ensure_tstat(NxgCtx* c, size_t words, NetidxError* err) {
-    if (words <= c->tstat_words) return true;
-    size_t n = std::max(words, c->tstat_words * 2);
-    n = std::max<size_t>(n, 4096);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->tstat) HIPCHK(hipFree(c->tstat));
-    c->tstat = nullptr;
-    HIPCHK(hipMalloc(&c->tstat, n * 8));
-    HIPCHK(hipMemsetAsync(c->tstat, 0, n * 8, c->stream));
-    c->tstat_words = n;
-    return true;
+    return grow(c, c->tstat, words, kGrowTileStatus, err);
 }
 
 bool ensure_escratch(NxgCtx* c, size_t words, NetidxError* err) {
-    if (words <= c->escratch_words) return true;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->escratch) HIPCHK(hipFree(c->escratch));
-    c->escratch = nullptr;
-    size_t n = std::max<size_t>(words, 1024);
-    HIPCHK(hipMalloc(&c->escratch, n * 8));
-    c->escratch_words = n;
-    return true;
+    return grow(c, c->escratch, words, kGrowEncScratch, err);
+}
+
+bool ensure_rdesc(NxgCtx* c, size_t bytes, NetidxError* err) {
+    return grow(c, c->rdesc, bytes, kGrowDouble64K, err);
+}
+
+bool ensure_glws(NxgCtx* c, size_t bytes, NetidxError* err) {
+    return grow(c, c->glws, bytes, kGrowDouble64K, err);
+}
+
+// An entry point that would overtake the async calls in flight refuses.
+bool no_pending(NxgCtx* c, NetidxError* err) {
+    if (c->pending.empty()) return true;
+    set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
+    return false;
 }
 
 bool is_device_ptr(const void* p) {
@@ -309,6 +310,18 @@ ColsDesc desc_of(const NxgColumns* c, const NxgWriteCols* w = nullptr) {
     return d;
 }
 
+void cols_free_impl(NxgColumns* c) {
+    void* ps[] = {c->id, c->tag, c->fixed, c->aux, c->ctag, c->cfixed, c->caux,
+                  c->ctl_row, c->ctl_off, c->ctl_len, c->ctl_variant};
+    for (void* p : ps) {
+        if (!p) continue;
+        if (c->mem == NXG_MEM_DEVICE) (void)hipFree(p);
+        else (void)hipHostFree(p);
+    }
+    memset(c, 0, sizeof *c);
+}
+
+// On failure nothing stays allocated and *o is all zero.
 bool cols_alloc_impl(uint32_t layout, uint64_t cr, uint64_t cc, uint64_t ck, uint32_t mem,
                      NxgColumns* o, NetidxError* err) {
     memset(o, 0, sizeof *o);
@@ -327,27 +340,16 @@ bool cols_alloc_impl(uint32_t layout, uint64_t cr, uint64_t cc, uint64_t ck, uin
         }
         return true;
     };
-    if (!alloc((void**)&o->id, cr * 8) || !alloc((void**)&o->fixed, cr * 8)) return false;
-    if (layout == NXG_LAYOUT_MIXED) {
-        if (!alloc((void**)&o->tag, cr) || !alloc((void**)&o->aux, cr * 4) ||
-            !alloc((void**)&o->ctag, cc) || !alloc((void**)&o->cfixed, cc * 8) ||
-            !alloc((void**)&o->caux, cc * 4) || !alloc((void**)&o->ctl_row, ck * 8) ||
-            !alloc((void**)&o->ctl_off, ck * 8) || !alloc((void**)&o->ctl_len, ck * 4) ||
-            !alloc((void**)&o->ctl_variant, ck))
-            return false;
+    bool ok = alloc((void**)&o->id, cr * 8) && alloc((void**)&o->fixed, cr * 8);
+    if (ok && layout == NXG_LAYOUT_MIXED) {
+        ok = alloc((void**)&o->tag, cr) && alloc((void**)&o->aux, cr * 4) &&
+             alloc((void**)&o->ctag, cc) && alloc((void**)&o->cfixed, cc * 8) &&
+             alloc((void**)&o->caux, cc * 4) && alloc((void**)&o->ctl_row, ck * 8) &&
+             alloc((void**)&o->ctl_off, ck * 8) && alloc((void**)&o->ctl_len, ck * 4) &&
+             alloc((void**)&o->ctl_variant, ck);
     }
-    return true;
-}
-
-void cols_free_impl(NxgColumns* c) {
-    void* ps[] = {c->id, c->tag, c->fixed, c->aux, c->ctag, c->cfixed, c->caux,
-                  c->ctl_row, c->ctl_off, c->ctl_len, c->ctl_variant};
-    for (void* p : ps) {
-        if (!p) continue;
-        if (c->mem == NXG_MEM_DEVICE) (void)hipFree(p);
-        else (void)hipHostFree(p);
-    }
-    memset(c, 0, sizeof *c);
+    if (!ok) cols_free_impl(o);
+    return ok;
 }
 
 // device staging columns shaped like `like` (grown on demand)
@@ -404,18 +406,6 @@ bool seq_active(const NxgCtx* c) {
     return !c->no_seq && !c->force_x && c->seq_left == 0 && c->irregular_left == 0;
 }
 
-bool ensure_rdesc(NxgCtx* c, size_t bytes, NetidxError* err) {
-    if (bytes <= c->rdesc_cap) return true;
-    size_t n = std::max(bytes, c->rdesc_cap * 2);
-    n = std::max<size_t>(n, 1 << 16);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->rdesc) HIPCHK(hipFree(c->rdesc));
-    c->rdesc = nullptr;
-    HIPCHK(hipMalloc(&c->rdesc, n));
-    c->rdesc_cap = n;
-    return true;
-}
-
 // the single-pass decoder of any f64 frame
 bool enqueue_dec_x(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* out, DevStatus* st,
                    NetidxError* err) {
@@ -451,23 +441,11 @@ bool enqueue_dec_fast(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* out
     return enqueue_dec_x(c, f, len, out, st, err);
 }
 
-bool ensure_glws(NxgCtx* c, size_t bytes, NetidxError* err) {
-    if (bytes <= c->glws_cap) return true;
-    size_t n = std::max(bytes, c->glws_cap * 2);
-    n = std::max<size_t>(n, 1 << 16);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->glws) HIPCHK(hipFree(c->glws));
-    c->glws = nullptr;
-    HIPCHK(hipMalloc(&c->glws, n));
-    c->glws_cap = n;
-    return true;
-}
-
 bool enqueue_dec_general(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* out,
                          DevStatus* st, NetidxError* err) {
     if (!ensure_glws(c, nxg_dec_gen_scratch_bytes(len), err)) return false;
     const ColsDesc d = desc_of(out);
-    HIPCHK(nxg_launch_dec_gen(f, len, d, c->glws, c->gruns,
+    HIPCHK(nxg_launch_dec_gen(f, len, d, reinterpret_cast<uint32_t*>(c->glws.get()), c->gruns,
                               c->gruns + (size_t)gdec2::MAX_RUNS * gdec2::RUN_WORDS,
                               c->wgs_dec_gen, st, c->stream));
     return true;
@@ -485,7 +463,7 @@ bool enqueue_dec_mixed(NxgCtx* c, const uint8_t* f, uint64_t len, NxgColumns* ou
         const uint64_t need = std::max(nxg_fmx_scratch_bytes(len), nxg_dec_gen_scratch_bytes(len));
         if (!ensure_glws(c, need, err)) return false;
         const bool lean = c->fmx_count_mode == 2 || (c->fmx_count_mode == 0 && !c->fmx_full);
-        HIPCHK(nxg_launch_dec_fmx(f, len, d, reinterpret_cast<uint8_t*>(c->glws), c->wgs_fmx, st,
+        HIPCHK(nxg_launch_dec_fmx(f, len, d, c->glws, c->wgs_fmx, st,
                                   c->stream, lean));
         return true;
     }
@@ -650,14 +628,7 @@ bool frame_to_device(NxgCtx* c, const uint8_t* frame, uint64_t len, const uint8_
         *df = frame;
         return true;
     }
-    if (c->dframe_cap < len + 16) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dframe) HIPCHK(hipFree(c->dframe));
-        c->dframe = nullptr;
-        size_t n = std::max<size_t>(len + 16, 1 << 20);
-        HIPCHK(hipMalloc(&c->dframe, n));
-        c->dframe_cap = n;
-    }
+    if (!grow(c, c->dframe, len + 16, kGrowFrame, err)) return false;
     if (len)
         HIPCHK(hipMemcpyAsync(c->dframe, frame, len,
                               dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
@@ -956,6 +927,59 @@ uint32_t nxg_debug_f64s_plan(uint32_t n, const uint64_t* wire, const uint64_t* l
     return launches;
 }
 
+// Not part of the ABI, and needs no GPU: one call of the grow routine every DevBuf uses
+// (nxg_devbuf.h, through the grow_with that reports production failures) against a scripted fake
+// of its four operations. The buffer comes in and goes out as *ptr / *cap (elements of `elem`
+// bytes, pinned: host memory); `policy` is the row of the policy table, 0 kGrowDouble to 8
+// kGrowFirstTable; fail_op is the operation that fails (0 none, 1 sync, 2 free, 3 alloc,
+// 4 memset). ops[i], args[i]: the operations issued, in order, at most 8 (1 sync; 2 free, the
+// pointer; 3 alloc, the bytes; 4 memset, the bytes; + 16 on pinned memory); *n_ops their count.
+bool nxg_debug_devbuf_grow(uint64_t* ptr, uint64_t* cap, uint32_t elem, bool pinned,
+                           uint32_t policy, uint64_t need, uint32_t fail_op, uint32_t* ops,
+                           uint64_t* args, uint32_t* n_ops, NetidxError* err) {
+    static const GrowPolicy rows[] = {kGrowDouble,     kGrowDouble64K, kGrowTileStatus,
+                                      kGrowEncScratch, kGrowFrame,     kGrowWriteCols,
+                                      kGrowZstdRecs,   kGrowZstdEnc,   kGrowFirstTable};
+    struct Fake {
+        uint32_t fail_op, *ops, n;
+        uint64_t* args;
+        int op(uint32_t code, DevMem m, uint64_t arg) {
+            if (n < 8) {
+                ops[n] = code + (m == DevMem::Pinned ? 16u : 0u);
+                args[n] = arg;
+            }
+            n++;
+            return code == fail_op ? 2 : 0;
+        }
+        int sync() { return op(1, DevMem::Device, 0); }
+        int free(void* p, DevMem m) { return op(2, m, (uintptr_t)p); }
+        int alloc(void** p, size_t bytes, DevMem m) {
+            const int e = op(3, m, bytes);
+            if (!e) *p = (void*)(uintptr_t)(0x7000000000ull + bytes);
+            return e;
+        }
+        int zero(void* p, size_t bytes) { return op(4, DevMem::Device, bytes); }
+        static const char* errstr(int) { return "scripted failure"; }
+    } fake{fail_op, ops, 0, args};
+    struct Raw {
+        DevBufState s;
+        size_t elem;
+        DevMem mem;
+        GrowFail grow(size_t need, GrowPolicy pol, Fake& f) {
+            return devbuf_grow_steps(s, elem, mem, need, pol, f);
+        }
+    } raw{{(void*)(uintptr_t)*ptr, (size_t)*cap}, elem, pinned ? DevMem::Pinned : DevMem::Device};
+    if (policy >= sizeof rows / sizeof rows[0]) {
+        set_err(err, "policy: no such row");
+        return false;
+    }
+    const bool ok = grow_with(raw, need, rows[policy], fake, err);
+    *ptr = (uintptr_t)raw.s.p;
+    *cap = raw.s.cap;
+    *n_ops = fake.n;
+    return ok;
+}
+
 // Not part of the ABI: the last fast archive attempt's FaHead (fast_fail | arrived << 32, end,
 // end_children, items, kids, recounts, decline reasons, 1 + the last declining tile).
 void nxg_debug_fa(NxgCtx* c, unsigned long long out[8]) {
@@ -1045,37 +1069,17 @@ void nxg_ctx_destroy(NxgCtx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->dcols_valid) cols_free_impl(&c->dcols);
-    if (c->tstat) (void)hipFree(c->tstat);
-    if (c->glws) (void)hipFree(c->glws);
     if (c->gruns) (void)hipFree(c->gruns);
-    if (c->dscratch) (void)hipFree(c->dscratch);
-    if (c->pscratch) (void)hipFree(c->pscratch);
-    if (c->dframe) (void)hipFree(c->dframe);
-    if (c->escratch) (void)hipFree(c->escratch);
-    if (c->rdesc) (void)hipFree(c->rdesc);
     if (c->zdefs) (void)hipFree(c->zdefs);
     if (c->zlit) (void)hipFree(c->zlit);
-    if (c->zrecs) (void)hipFree(c->zrecs);
     if (c->zc_tables) (void)hipFree(c->zc_tables);
     if (c->zc_slab) (void)hipFree(c->zc_slab);
-    if (c->zc_recs) (void)hipFree(c->zc_recs);
-    if (c->zc_out) (void)hipFree(c->zc_out);
-    if (c->zc_pack) (void)hipFree(c->zc_pack);
-    if (c->zc_hpin) (void)hipHostFree(c->zc_hpin);
     for (hipEvent_t e : c->zc_ev)
         if (e) (void)hipEventDestroy(e);
-    if (c->dheap) (void)hipFree(c->dheap);
-    if (c->aw_dev) (void)hipFree(c->aw_dev);
-    if (c->aw_host) (void)hipHostFree(c->aw_host);
-    if (c->dwflags) (void)hipFree(c->dwflags);
-    if (c->dwid) (void)hipFree(c->dwid);
-    if (c->rw_first) (void)hipFree(c->rw_first);
-    if (c->rr_first_id) (void)hipFree(c->rr_first_id);
-    if (c->rr_first_q) (void)hipFree(c->rr_first_q);
     if (c->dst) (void)hipFree(c->dst);
     if (c->hst) (void)hipHostFree(c->hst);
     if (c->own) (void)hipStreamDestroy(c->own);
-    delete c;
+    delete c;  // (every grow-on-demand buffer: the DevBuf members free themselves)
 }
 
 bool nxg_ctx_set_stream(NxgCtx* c, void* s, NetidxError* err) {
@@ -1106,11 +1110,7 @@ bool nxg_columns_alloc(NxgCtx* c, uint32_t layout, uint64_t cap_rows, uint64_t c
         return false;
     }
     if (!set_device(c, err)) return false;
-    if (!cols_alloc_impl(layout, cap_rows, cap_children, cap_ctl, mem, out, err)) {
-        cols_free_impl(out);
-        return false;
-    }
-    return true;
+    return cols_alloc_impl(layout, cap_rows, cap_children, cap_ctl, mem, out, err);
 }
 
 void nxg_columns_free(NxgCtx* c, NxgColumns* cols) {
@@ -1125,10 +1125,7 @@ bool nxg_decode_updates(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgColumn
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (len >= (1ull << 40)) {
         set_err(err, "frame too large (%llu bytes)", (unsigned long long)len);
         return false;
@@ -1486,19 +1483,12 @@ bool nxg_ctx_sync(NxgCtx* c, NxgStatus* ust, NetidxError* err) {
 }
 
 // Grows the device staging of a host-resident NxgWriteCols to `rows` rows.
+// (at least one row: a decode into columns of capacity 0 still hands the kernels staged arrays,
+// which they refuse when null; growing for a need of 0 would leave an empty buffer empty)
 static bool ensure_dwcols(NxgCtx* c, uint64_t rows, NetidxError* err) {
-    if (c->dw_cap >= rows && c->dwflags) return true;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->dwflags) HIPCHK(hipFree(c->dwflags));
-    if (c->dwid) HIPCHK(hipFree(c->dwid));
-    c->dwflags = nullptr;
-    c->dwid = nullptr;
-    c->dw_cap = 0;
-    const size_t n = std::max<size_t>(rows, 1024);
-    HIPCHK(hipMalloc(&c->dwflags, n));
-    HIPCHK(hipMalloc(&c->dwid, n * 8));
-    c->dw_cap = n;
-    return true;
+    rows = std::max<uint64_t>(rows, 1);
+    return grow(c, c->dwflags, rows, kGrowWriteCols, err) &&
+           grow(c, c->dwid, rows, kGrowWriteCols, err);
 }
 
 // win: the rows are To::Write messages (nxg_encode_writes), else From::Update
@@ -1509,10 +1499,7 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     const bool host = in->mem == NXG_MEM_HOST || !is_device_ptr(in->id);
     const NxgColumns* din = in;
@@ -1553,14 +1540,7 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
             for (uint64_t i = 0; i < in->n_ctl; i++)
                 hi = std::max<uint64_t>(hi, in->ctl_off[i] + in->ctl_len[i]);
             heap_len = hi;
-            if (c->dheap_cap < heap_len + 16) {
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (c->dheap) HIPCHK(hipFree(c->dheap));
-                c->dheap = nullptr;
-                size_t n = std::max<size_t>(heap_len + 16, 1 << 20);
-                HIPCHK(hipMalloc(&c->dheap, n));
-                c->dheap_cap = n;
-            }
+            if (!grow(c, c->dheap, heap_len + 16, kGrowFrame, err)) return false;
             if (heap_len)
                 HIPCHK(hipMemcpyAsync(c->dheap, heap, heap_len, hipMemcpyHostToDevice, c->stream));
             dheap = c->dheap;
@@ -1592,14 +1572,7 @@ static bool encode_impl(NxgCtx* c, const NxgColumns* in, const uint8_t* heap, ui
                     (unsigned long long)total, (unsigned long long)cap);
             return false;
         }
-        if (host && c->dframe_cap < total + 16) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (c->dframe) HIPCHK(hipFree(c->dframe));
-            c->dframe = nullptr;
-            size_t n = std::max<size_t>(total + 16, 1 << 20);
-            HIPCHK(hipMalloc(&c->dframe, n));
-            c->dframe_cap = n;
-        }
+        if (host && !grow(c, c->dframe, total + 16, kGrowFrame, err)) return false;
         if (host) dout = c->dframe;
         cap = total;
     }
@@ -1632,10 +1605,7 @@ bool nxg_encode_archive_batch(NxgCtx* c, const NxgColumns* in, const uint8_t* he
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (in->mem != NXG_MEM_DEVICE || !mixed_capable(in) || in->n_ctl ||
         (in->n_rows && (!in->id || !is_device_ptr(in->id)))) {
         set_err(err, "archive batches encode from device MIXED-layout columns without control "
@@ -1748,10 +1718,7 @@ bool nxg_archive_decompress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* s
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (is_device_ptr(src)) {
         set_err(err, "the records must be in host memory (the archive's mmap)");
         return false;
@@ -1822,14 +1789,8 @@ bool nxg_archive_decompress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* s
     }
     const size_t rb = nxg_zstd_rec_bytes(), sb = nxg_zstd_res_bytes();
     static_assert(sizeof(Rec) == 32, "NxzRec layout");
-    if (c->zrecs_cap < (size_t)n * (rb + sb)) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->zrecs) HIPCHK(hipFree(c->zrecs));
-        c->zrecs = nullptr;
-        c->zrecs_cap = std::max<size_t>((size_t)n * (rb + sb), 1 << 16);
-        HIPCHK(hipMalloc(&c->zrecs, c->zrecs_cap));
-    }
-    uint8_t* drecs = static_cast<uint8_t*>(c->zrecs);
+    if (!grow(c, c->zrecs, (size_t)n * (rb + sb), kGrowZstdRecs, err)) return false;
+    uint8_t* drecs = c->zrecs;
     uint8_t* dres = drecs + (size_t)n * rb;
     const uint8_t* dsrc;
     if (!frame_to_device(c, src, src_len, &dsrc, err)) return false;
@@ -1886,18 +1847,6 @@ static bool zstd_dict_enc_ready(NxgCtx* c, NxgZstdDict* d, NetidxError* err) {
     return true;
 }
 
-static bool grow_dev(NxgCtx* c, uint8_t** p, size_t* cap, size_t need, NetidxError* err) {
-    if (*cap >= need) return true;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (*p) HIPCHK(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    const size_t n = std::max<size_t>(need + need / 4, 1 << 16);
-    HIPCHK(hipMalloc(p, n));
-    *cap = n;
-    return true;
-}
-
 bool nxg_archive_compress(NxgCtx* c, const NxgZstdDict* dict, const uint8_t* src,
                           uint64_t src_len, NxgArchiveRecord* recs, uint32_t n, bool indexed,
                           uint8_t* out, uint64_t cap, uint64_t* need, NetidxError* err) {
@@ -1922,10 +1871,7 @@ bool nxg_archive_compress_opts(NxgCtx* c, const NxgZstdDict* dict, const uint8_t
         set_err(err, "NxgZstdCompressOpts.reserved must be zero");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (is_device_ptr(src) || (out && is_device_ptr(out))) {
         set_err(err, "the records and the output must be in host memory");
         return false;
@@ -2017,9 +1963,8 @@ bool nxg_archive_compress_opts(NxgCtx* c, const NxgZstdDict* dict, const uint8_t
     }
     const size_t rb = nxg_zstd_enc_rec_bytes(), sb = nxg_zstd_enc_res_bytes();
     static_assert(sizeof(Rec) == 32 && sizeof(Res) == 16, "NxzEncRec / NxzEncRes layout");
-    if (!grow_dev(c, &c->zc_recs, &c->zc_recs_cap, (size_t)n * (rb + sb + 8 + 4) + 8, err))
-        return false;
-    if (!grow_dev(c, &c->zc_out, &c->zc_out_cap, dtotal, err)) return false;
+    if (!grow(c, c->zc_recs, (size_t)n * (rb + sb + 8 + 4) + 8, kGrowZstdEnc, err)) return false;
+    if (!grow(c, c->zc_out, dtotal, kGrowZstdEnc, err)) return false;
     uint8_t* drecs = c->zc_recs;
     uint8_t* dres = drecs + (size_t)n * rb;
     uint64_t* dpk = reinterpret_cast<uint64_t*>(dres + (size_t)n * sb);
@@ -2062,15 +2007,8 @@ bool nxg_archive_compress_opts(NxgCtx* c, const NxgZstdDict* dict, const uint8_t
         pk[i] = packed;
         packed += hr[i].out_len;
     }
-    if (!grow_dev(c, &c->zc_pack, &c->zc_pack_cap, packed, err)) return false;
-    if (c->zc_hpin_cap < packed) {
-        if (c->zc_hpin) HIPCHK(hipHostFree(c->zc_hpin));
-        c->zc_hpin = nullptr;
-        c->zc_hpin_cap = 0;
-        const size_t hn = std::max<size_t>(packed + packed / 4, 1 << 16);
-        HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&c->zc_hpin), hn, hipHostMallocDefault));
-        c->zc_hpin_cap = hn;
-    }
+    if (!grow(c, c->zc_pack, packed, kGrowZstdEnc, err)) return false;
+    if (!grow(c, c->zc_hpin, packed, kGrowZstdEnc, err)) return false;
     uint8_t* hp = c->zc_hpin;
     HIPCHK(hipMemcpyAsync(dpk, pk.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(nxg_launch_zstd_pack(c->zc_out, drecs, dres, dpk, n, c->zc_pack, c->ncu, c->stream));
@@ -2137,10 +2075,7 @@ bool nxg_decode_archive_batch(NxgCtx* c, const uint8_t* buf, uint64_t len, NxgCo
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (len >= (1ull << 40)) {
         set_err(err, "batch too large (%llu bytes)", (unsigned long long)len);
         return false;
@@ -2164,14 +2099,7 @@ bool nxg_decode_archive_batch(NxgCtx* c, const uint8_t* buf, uint64_t len, NxgCo
         for (;;) {
             if (!frame_to_device(c, buf, W, &df, err)) return false;
             const size_t need = nxg_fa_scratch_bytes(W);
-            if (need > c->dscratch_cap) {
-                HIPCHK(hipStreamSynchronize(c->stream));
-                if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-                c->dscratch = nullptr;
-                const size_t sz = std::max(need, c->dscratch_cap * 2);
-                HIPCHK(hipMalloc(&c->dscratch, sz));
-                c->dscratch_cap = sz;
-            }
+            if (!ensure_dscratch(c, need, err)) return false;
             HIPCHK(nxg_launch_dec_fa(df, W, p0, count, desc_of(out), c->dscratch, hh, nullptr,
                                      c->stream));
             HIPCHK(hipStreamSynchronize(c->stream));
@@ -2198,15 +2126,8 @@ bool nxg_decode_archive_batch(NxgCtx* c, const uint8_t* buf, uint64_t len, NxgCo
     }
     if (!frame_to_device(c, buf, len, &df, err)) return false;
     const size_t need = 64 + nxg_arch_scratch_bytes(len);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
-    uint32_t* cap_flag = reinterpret_cast<uint32_t*>(c->dscratch);
+    if (!ensure_dscratch(c, need, err)) return false;
+    uint32_t* cap_flag = reinterpret_cast<uint32_t*>(c->dscratch.get());
     HIPCHK(hipMemsetAsync(cap_flag, 0, 4, c->stream));
     NxgArchResult r{};
     HIPCHK(nxg_arch_decode(df, len, desc_of(out), c->dscratch + 64, cap_flag, 8, &r, c->stream));
@@ -2228,25 +2149,8 @@ bool nxg_decode_archive_batch(NxgCtx* c, const uint8_t* buf, uint64_t len, NxgCo
 // ---- a window of archive records and its image (nxg_archive_window.hip) -----------------------
 namespace {
 bool ensure_aw(NxgCtx* c, size_t dev_bytes, size_t host_bytes, NetidxError* err) {
-    if (dev_bytes > c->aw_dev_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->aw_dev) HIPCHK(hipFree(c->aw_dev));
-        c->aw_dev = nullptr;
-        const size_t sz = std::max(dev_bytes, c->aw_dev_cap * 2);
-        c->aw_dev_cap = 0;
-        HIPCHK(hipMalloc(&c->aw_dev, sz));
-        c->aw_dev_cap = sz;
-    }
-    if (host_bytes > c->aw_host_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->aw_host) HIPCHK(hipHostFree(c->aw_host));
-        c->aw_host = nullptr;
-        const size_t sz = std::max(host_bytes, c->aw_host_cap * 2);
-        c->aw_host_cap = 0;
-        HIPCHK(hipHostMalloc(&c->aw_host, sz, hipHostMallocDefault));
-        c->aw_host_cap = sz;
-    }
-    return true;
+    return grow(c, c->aw_dev, dev_bytes, kGrowDouble, err) &&
+           grow(c, c->aw_host, host_bytes, kGrowDouble, err);
 }
 
 // the ctx's scratch columns for one record of `len` bytes on the single-batch decoder (rows <=
@@ -2297,10 +2201,7 @@ bool nxg_archive_decode_window(NxgCtx* c, const uint8_t* dbuf, uint64_t buf_len,
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     if (buf_len && !is_device_ptr(dbuf)) {
         set_err(err, "the window's buffer must be device memory");
@@ -2315,7 +2216,7 @@ bool nxg_archive_decode_window(NxgCtx* c, const uint8_t* dbuf, uint64_t buf_len,
     if (n == 0) return true;
     const size_t bytes = sizeof(AwHead) + (size_t)n * sizeof(AwRec);
     if (!ensure_aw(c, bytes, bytes, err)) return false;
-    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host);
+    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host.get());
     AwRec* hr = reinterpret_cast<AwRec*>(c->aw_host + sizeof(AwHead));
     uint8_t* dhead = c->aw_dev;
     uint8_t* drecs = c->aw_dev + sizeof(AwHead);
@@ -2433,10 +2334,7 @@ bool nxg_archive_build_image(NxgCtx* c, const NxgColumns* window, uint64_t n_ids
         set_err(err, "null argument");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     if ((rows && !is_device_ptr(window->id)) || (out->cap_rows && !is_device_ptr(out->id)) ||
         (keep && !is_device_ptr(keep))) {
@@ -2449,7 +2347,7 @@ bool nxg_archive_build_image(NxgCtx* c, const NxgColumns* window, uint64_t n_ids
     HIPCHK(nxg_launch_aw_image(desc_of(window), rows, n_ids, keep, c->aw_dev + sizeof(AwHead),
                                out->cap_rows, out->id, out->tag, out->fixed, out->aux,
                                out->src_row, c->aw_dev, c->stream));
-    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host);
+    AwHead* hh = reinterpret_cast<AwHead*>(c->aw_host.get());
     HIPCHK(hipMemcpyAsync(hh, c->aw_dev, sizeof(AwHead), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     if (n_ids == 0 && rows) hh->bad_row = 0;  // every Id is past an empty table
@@ -2489,20 +2387,10 @@ bool nxg_partition_by_tag(NxgCtx* c, const NxgColumns* cols, NxgTagView* out, Ne
         set_err(err, "the type-partitioned view needs device columns and device outputs");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     const size_t need = nxg_part_scratch_bytes(n);
-    if (need > c->pscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->pscratch) HIPCHK(hipFree(c->pscratch));
-        c->pscratch = nullptr;
-        const size_t m = std::max(need, c->pscratch_cap * 2);
-        HIPCHK(hipMalloc(&c->pscratch, m));
-        c->pscratch_cap = m;
-    }
+    if (!grow(c, c->pscratch, need, kGrowDouble, err)) return false;
     uint64_t* doff = nullptr;
     HIPCHK(nxg_launch_partition(cols->tag, cols->fixed, cols->aux, n, c->pscratch, out->rank,
                                 out->row_of, out->fixed, out->aux, &doff, c->stream));
@@ -2534,15 +2422,8 @@ bool nxg_dispatch_updates(NxgCtx* c, const NxgSubTable* tab, const uint64_t* id,
     }
     HIPCHK(hipSetDevice(c->device));
     const size_t need = 64 + nxg_disp_scratch_bytes(n_rows, tab->n_chans);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t n = std::max(need, c->dscratch_cap * 2);
-        HIPCHK(hipMalloc(&c->dscratch, n));
-        c->dscratch_cap = n;
-    }
-    uint64_t* um = reinterpret_cast<uint64_t*>(c->dscratch);
+    if (!ensure_dscratch(c, need, err)) return false;
+    uint64_t* um = reinterpret_cast<uint64_t*>(c->dscratch.get());
     HIPCHK(nxg_launch_dispatch(*tab, id, n_rows, c->dscratch + 64, out->chan_off, out->ent_sub,
                                out->ent_row, out->cap_entries, out->last_row, um, c->ncu,
                                c->stream));
@@ -2586,14 +2467,7 @@ bool nxg_publish_commit(NxgCtx* c, const NxgPubTable* tab, const NxgColumns* bat
     HIPCHK(hipSetDevice(c->device));
     const size_t pub = (nxg_pub_scratch_bytes(n, tab->n_slots) + 255) & ~size_t(255);
     const size_t need = pub + 64 + nxg_disp_scratch_bytes(n, tab->n_clients);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     const NxgPubBatch b{batch->id,    batch->tag,   batch->fixed, batch->aux, batch->ctag,
                         batch->cfixed, batch->caux, heap,         kind,       n};
     HIPCHK(nxg_launch_pub_stage1(*tab, b, c->dscratch, c->ncu, c->stream));
@@ -2666,14 +2540,7 @@ bool nxg_publish_unsubscribes(NxgCtx* c, const uint64_t* id, const uint32_t* cli
     HIPCHK(hipSetDevice(c->device));
     const size_t mode_bytes = (n + 255) & ~uint64_t(255);
     const size_t need = mode_bytes + 64 + nxg_disp_scratch_bytes(n, n_clients);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     uint8_t* mode = c->dscratch;
     if (n) HIPCHK(hipMemsetAsync(mode, 2, n, c->stream));
     const NxgSubTable st{0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, n_clients};
@@ -2725,10 +2592,7 @@ bool nxg_encode_clients(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
                      "arrays, out->out and out->client_off)");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     out->n_bytes = 0;
     const uint64_t cnt = (uint64_t)n_clients + 1;
@@ -2884,10 +2748,7 @@ bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
             return false;
         }
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     out->n_bytes = out->n_items = out->n_dropped = 0;
     if (ne == 0) {  // no entries: no record, and no kernel runs
@@ -2917,15 +2778,7 @@ bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
     a.rec_off = out->rec_off;
     a.rec_items = out->rec_items;
     const size_t need = nxg_rec_scratch_bytes(ne, n_chans);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        c->dscratch_cap = 0;
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     NxgRecHead h;
     HIPCHK(nxg_launch_record(a, c->dscratch, c->stream));
     HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -3121,15 +2974,7 @@ bool vt_run(NxgCtx* c, NxgVtArgs a, uint64_t seg_cap, NxgVtHead* h, NetidxError*
     for (int attempt = 0;; attempt++) {
         const size_t need = nxg_vt_scratch_bytes(a.dst.n_slots, seg_cap,
                                                  a.dst.tag ? kVtPathMixed : kVtPathF64);
-        if (need > c->dscratch_cap) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-            c->dscratch = nullptr;
-            const size_t sz = std::max(need, c->dscratch_cap * 2);
-            c->dscratch_cap = 0;
-            HIPCHK(hipMalloc(&c->dscratch, sz));
-            c->dscratch_cap = sz;
-        }
+        if (!ensure_dscratch(c, need, err)) return false;
         a.seg_cap = seg_cap;
         HIPCHK(nxg_launch_vt_apply(a, c->dscratch, c->ncu, c->stream));
         HIPCHK(hipMemcpyAsync(h, c->dscratch, sizeof *h, hipMemcpyDeviceToHost, c->stream));
@@ -3142,10 +2987,7 @@ bool vt_run(NxgCtx* c, NxgVtArgs a, uint64_t seg_cap, NxgVtHead* h, NetidxError*
 }
 
 bool vt_entry(NxgCtx* c, NetidxError* err) {
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     return set_device(c, err);
 }
 }  // namespace
@@ -3310,15 +3152,7 @@ bool nxg_value_table_set_unsubscribed(NxgCtx* c, NxgValueTable* t, const uint32_
     a.old = vt_src_of_table(t);
     a.dst = vt_dst(t, false);
     const size_t need = nxg_vt_scratch_bytes(t->n_slots, 0, kVtPathUnsub);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        c->dscratch_cap = 0;
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     HIPCHK(nxg_launch_vt_unsub(a, slot, n, c->dscratch, c->stream));
     NxgVtHead h{};
     HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
@@ -3422,10 +3256,7 @@ bool nxg_decode_writes_opts(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgCo
         set_err(err, "columns and write columns must both be device or both pinned host memory");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (len >= (1ull << 40)) {
         set_err(err, "frame too large (%llu bytes)", (unsigned long long)len);
         return false;
@@ -3465,7 +3296,7 @@ bool nxg_decode_writes_opts(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgCo
                               err);
         if (ok) {
             const ColsDesc d = desc_of(target, &wtarget);
-            const hipError_t le = nxg_launch_dec_wfast(df, len, d, reinterpret_cast<uint8_t*>(c->glws),
+            const hipError_t le = nxg_launch_dec_wfast(df, len, d, c->glws,
                                                        st, c->stream);
             if (le != hipSuccess) {
                 set_err(err, "fast To decode launch failed: %s", hipGetErrorString(le));
@@ -3484,7 +3315,7 @@ bool nxg_decode_writes_opts(NxgCtx* c, const uint8_t* frame, uint64_t len, NxgCo
         if (ok) {
             const ColsDesc d = desc_of(target, &wtarget);
             const hipError_t le =
-                nxg_launch_dec_gen(df, len, d, c->glws, c->gruns,
+                nxg_launch_dec_gen(df, len, d, reinterpret_cast<uint32_t*>(c->glws.get()), c->gruns,
                                    c->gruns + (size_t)gdec2::MAX_RUNS * gdec2::RUN_WORDS,
                                    c->wgs_dec_gen, st, c->stream, true);
             if (le != hipSuccess) {
@@ -3632,38 +3463,18 @@ bool nxg_route_writes(NxgCtx* c, const NxgWriteTable* tab, const uint8_t* frame,
         set_err(err, "out: null output array");
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     HIPCHK(hipSetDevice(c->device));
     // the first-unsubscribe table: grown (and cleared) on demand, never cleared per call
-    if (tab->n_ids > c->rw_first_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->rw_first) HIPCHK(hipFree(c->rw_first));
-        c->rw_first = nullptr;
-        c->rw_first_cap = 0;
-        const size_t n = std::max<size_t>(tab->n_ids, 4096);
-        HIPCHK(hipMalloc(&c->rw_first, n * 8));
-        HIPCHK(hipMemsetAsync(c->rw_first, 0, n * 8, c->stream));
-        c->rw_first_cap = n;
-    }
+    if (!grow(c, c->rw_first, tab->n_ids, kGrowFirstTable, err)) return false;
     if (++c->rw_epoch >= (1u << 24)) {  // wrap: stale words could alias epoch 1 again
         c->rw_epoch = 1;
-        if (c->rw_first) HIPCHK(hipMemsetAsync(c->rw_first, 0, c->rw_first_cap * 8, c->stream));
+        if (c->rw_first) HIPCHK(hipMemsetAsync(c->rw_first, 0, c->rw_first.cap() * 8, c->stream));
     }
     const size_t rw = (nxg_rw_scratch_bytes(rows, spans) + 255) & ~size_t(255);
     const size_t last = (tab->n_slots * 8 + 255) & ~size_t(255);
     const size_t need = rw + last + 64 + nxg_disp_scratch_bytes(rows, tab->n_chans);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        c->dscratch_cap = 0;
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     NxgRwArgs a{};
     a.tab = *tab;
     a.frame = frame;
@@ -3731,8 +3542,7 @@ struct NxgPathTable {
     uint64_t heap_used = 0;  // bytes of the heap handed out (removed paths' bytes included)
     uint64_t used = 0;       // slots that are not empty: live + tombstones
     NxgPtView v{};
-    uint8_t* stage = nullptr;  // per-call device staging, grown on demand
-    size_t stage_cap = 0;
+    DevBuf<uint8_t> stage;  // per-call device staging, grown on demand
 };
 
 namespace {
@@ -3760,15 +3570,7 @@ bool pt_alloc_arrays(NxgCtx* c, uint64_t slots, NxgPtView* v, NetidxError* err) 
 }
 
 bool pt_stage(NxgCtx* c, NxgPathTable* t, size_t need, NetidxError* err) {
-    if (need <= t->stage_cap) return true;
-    const size_t sz = std::max(need, t->stage_cap * 2);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (t->stage) HIPCHK(hipFree(t->stage));
-    t->stage = nullptr;
-    t->stage_cap = 0;
-    HIPCHK(hipMalloc(&t->stage, sz));
-    t->stage_cap = sz;
-    return true;
+    return grow(c, t->stage, need, kGrowDouble, err);
 }
 
 // the call's path list: offsets ascending, every path shorter than 2^32 bytes
@@ -3791,11 +3593,7 @@ bool pt_call_ok(NxgCtx* c, const NxgPathTable* t, NetidxError* err) {
         set_err(err, "the path table belongs to device %d, the ctx to %d", t->device, c->device);
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
-    return true;
+    return no_pending(c, err);
 }
 
 size_t up256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -3839,7 +3637,6 @@ void nxg_path_table_free(NxgPathTable* t) {
     if (!t) return;
     (void)hipSetDevice(t->device);
     pt_free_arrays(&t->v, true);
-    if (t->stage) (void)hipFree(t->stage);
     delete t;
 }
 
@@ -4050,10 +3847,7 @@ bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t
                 c->device);
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     out->n_spans = out->n_sub = out->n_deferred = out->n_replies = out->reply_len = 0;
     for (int o = 0; o < 5; o++) out->n_outcome[o] = 0;
     out->next_ctl = ctl_begin;
@@ -4102,15 +3896,7 @@ bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t
     }
     HIPCHK(hipSetDevice(c->device));
     const size_t need = nxg_rs_scratch_bytes(spans);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        c->dscratch_cap = 0;
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     NxgRsArgs a{};
     a.paths = tab->paths->v;
     a.cur.tag = const_cast<uint8_t*>(pub->cur_tag);
@@ -4181,22 +3967,6 @@ bool nxg_route_subscribes(NxgCtx* c, const NxgSubscribeTable* tab, const uint8_t
 }
 
 // ---- reply routing (subscriber/connection.rs:67-83, 409-541) ------------------------------------
-namespace {
-// an epoch-tagged table of the ctx, grown (and cleared) on demand, never cleared per call
-bool rr_table(NxgCtx* c, uint64_t** tab, size_t* cap, uint64_t want, NetidxError* err) {
-    if (want <= *cap) return true;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (*tab) HIPCHK(hipFree(*tab));
-    *tab = nullptr;
-    *cap = 0;
-    const size_t n = std::max<size_t>(want, 4096);
-    HIPCHK(hipMalloc(tab, n * 8));
-    HIPCHK(hipMemsetAsync(*tab, 0, n * 8, c->stream));
-    *cap = n;
-    return true;
-}
-}  // namespace
-
 // Replaces process_batch: nxg_route_replies.hip's passes, the dispatch of nxg_dispatch.hip over the
 // call's items for the fan-out, one copy of the head, one synchronisation.
 bool nxg_route_replies(NxgCtx* c, const NxgReplyTable* tab, const uint8_t* frame,
@@ -4296,32 +4066,22 @@ bool nxg_route_replies(NxgCtx* c, const NxgReplyTable* tab, const uint8_t* frame
             return false;
         }
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     HIPCHK(hipSetDevice(c->device));
-    if (!rr_table(c, &c->rr_first_id, &c->rr_first_id_cap, st->n_ids, err) ||
-        !rr_table(c, &c->rr_first_q, &c->rr_first_q_cap, tab->n_pending, err))
+    // the epoch-tagged tables: grown (and cleared) on demand, never cleared per call
+    if (!grow(c, c->rr_first_id, st->n_ids, kGrowFirstTable, err) ||
+        !grow(c, c->rr_first_q, tab->n_pending, kGrowFirstTable, err))
         return false;
     if (++c->rr_epoch >= (1u << 24)) {  // wrap: stale words could alias epoch 1 again
         c->rr_epoch = 1;
         if (c->rr_first_id)
-            HIPCHK(hipMemsetAsync(c->rr_first_id, 0, c->rr_first_id_cap * 8, c->stream));
+            HIPCHK(hipMemsetAsync(c->rr_first_id, 0, c->rr_first_id.cap() * 8, c->stream));
         if (c->rr_first_q)
-            HIPCHK(hipMemsetAsync(c->rr_first_q, 0, c->rr_first_q_cap * 8, c->stream));
+            HIPCHK(hipMemsetAsync(c->rr_first_q, 0, c->rr_first_q.cap() * 8, c->stream));
     }
     const size_t rr = (nxg_rr_scratch_bytes(rows, spans) + 255) & ~size_t(255);
     const size_t need = rr + 64 + nxg_disp_scratch_bytes(rows + spans, st->n_chans);
-    if (need > c->dscratch_cap) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (c->dscratch) HIPCHK(hipFree(c->dscratch));
-        c->dscratch = nullptr;
-        const size_t sz = std::max(need, c->dscratch_cap * 2);
-        c->dscratch_cap = 0;
-        HIPCHK(hipMalloc(&c->dscratch, sz));
-        c->dscratch_cap = sz;
-    }
+    if (!ensure_dscratch(c, need, err)) return false;
     NxgRrArgs a{};
     a.subs = *st;
     a.pending = tab->pending->v;
@@ -4476,10 +4236,7 @@ bool nxg_decode_range(NxgCtx* c, const uint8_t* dframe, uint64_t W, uint64_t beg
                 (unsigned long long)end, (unsigned long long)W);
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (out->mem != NXG_MEM_DEVICE || !is_device_ptr(dframe)) {
         set_err(err, "range decode needs a device frame and device columns");
         return false;
@@ -4567,7 +4324,7 @@ bool nxg_decode_range(NxgCtx* c, const uint8_t* dframe, uint64_t W, uint64_t beg
         bool ok2 = ensure_glws(c, nxg_fmx_scratch_bytes(R), err);
         if (ok2) {
             const hipError_t e = nxg_launch_dec_fmx_range(dframe, W, begin, end, d,
-                                                          reinterpret_cast<uint8_t*>(c->glws),
+                                                          c->glws,
                                                           c->wgs_fmx, st2, c->stream);
             if (e != hipSuccess) {
                 set_err(err, "range decode launch: %s", hipGetErrorString(e));
@@ -4658,10 +4415,7 @@ bool nxg_decode_share(NxgCtx* c, const uint8_t* dframe, uint64_t W, uint32_t sha
         set_err(err, "bad argument (share %u of %u)", share, shares);
         return false;
     }
-    if (!c->pending.empty()) {
-        set_err(err, "an async operation is pending on this ctx; call nxg_ctx_sync first");
-        return false;
-    }
+    if (!no_pending(c, err)) return false;
     if (W >= (1ull << 40)) {
         set_err(err, "frame too large (%llu bytes)", (unsigned long long)W);
         return false;
