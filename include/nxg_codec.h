@@ -1281,6 +1281,94 @@ bool nxg_archive_build_image(NxgCtx* ctx, const NxgColumns* window, uint64_t n_i
                              const uint8_t* keep /* [n_ids] device, NULL = every Id */,
                              NxgArchiveImage* out, NetidxError* err);
 
+/* ---- playback: replaces the loop of the recorder's publish session over a batch (netidx-archive/
+ * src/recorder/publish/session_shard.rs:196-245, process_batch) and over the pathmap (reimage,
+ * session_shard.rs:375-409). For every BatchItem(id, ev) the reference turns Event::Unsubscribed
+ * into Value::Null, looks the archive Id up in `published: FxHashMap<Id, Val>` (session_shard.rs:42),
+ * calls val.update(&mut pbatch, v) on a hit, publishes the path on a miss when it has one and the
+ * session's filter matches it, and drops anything else; then pbatch.commit. Here a decoded window
+ * becomes the update rows of all its records in one call, in the form nxg_publish_commit,
+ * nxg_encode_clients and nxg_value_table_apply take.
+ * `window` and `info` are what nxg_archive_decode_window produced (info: host memory, n_recs
+ * entries; only row_off and n_rows are read). Record i's rows are window rows [info[i].row_off, +
+ * info[i].n_rows); a sub-range of the infos (info + k, n_recs - k) is as good as all of them.
+ * Window rows in front of, between or behind the records belong to none: they are neither read,
+ * kept nor counted.
+ * The table is `published` with the host's knowledge folded in: pub_id_of_arch[a] is the publisher
+ * Id of archive Id a, NXG_REPLAY_DROP when a has no path or the session's filter does not match it
+ * (the reference's silent drop), or NXG_REPLAY_MISS when it has a path the filter matches and is
+ * not published yet.
+ * Row by row in window order, with a = window->id[r]:
+ *   miss: a >= tab->n_ids, or the table holds NXG_REPLAY_MISS (the reference would call
+ *     path_for_id here, the host's knowledge);
+ *   drop: the table holds NXG_REPLAY_DROP; counted in n_dropped;
+ *   kept: anything else. The output row is (id = pub_id_of_arch[a], tag, fixed, aux, src_row = r):
+ *     tag NXG_TAG_UNSUBSCRIBED becomes Value::Null (tag 16, fixed 0, aux 0), every other value is
+ *     copied verbatim -- container `fixed` still indexes the window's child arrays and text `fixed`
+ *     still indexes dbuf. An NxgColumns made of the row arrays (n_rows, cap_rows) and the window's
+ *     child arrays is a batch for nxg_publish_commit(..., heap = dbuf, ...), as the image's is for
+ *     the encoder.
+ * The call stops in front of a miss, as nxg_route_writes stops in front of a Subscribe: publishing
+ * is the host's job and changes the table for every later item. n_done is the lowest record that
+ * holds a miss, or n_recs when none does, whatever the scheduling. Records [0, n_done) are emitted
+ * and nothing of later records is: record i's updates are rows [rec_off[i], rec_off[i+1]),
+ * rec_off[0] == 0, rec_off[i] == rec_off[n_done] for i > n_done, n_rows == rec_off[n_recs], and
+ * n_dropped counts the drops of records [0, n_done) only. miss_row[0 .. min(n_miss, cap_miss))
+ * lists the window rows of record n_done that missed, in item order; n_miss is their true count
+ * (0 when n_done == n_recs). The caller publishes those Ids (publisher.publish(path, v), the first
+ * row per Id), updates its table and calls again from record n_done (info + n_done, n_recs -
+ * n_done). On that second call the publishing row comes back as an Update of a value that equals
+ * `current` and has no subscriber yet, which changes neither a client's bytes nor `current`: the
+ * protocol is observably the reference's. After reimage has published the pathmap, misses happen
+ * only when a live recording adds paths, so the stop is rare; it costs a second small launch and
+ * read-back.
+ * Val::update is NXG_PUB_UPDATE: whether a row is sent does not depend on `current`. One
+ * nxg_publish_commit over rows [0, n_rows) therefore gives every client the concatenation, in
+ * record order, of what per-record commits give, and its last_row is the last per-record one
+ * shifted by rec_off. Speed::Unlimited commits a window at once; Speed::Limited commits
+ * per-record views, the same arrays at pointer offset rec_off[i].
+ * false with a message:
+ *   on misuse, before any launch: a null argument, columns that are not device MIXED columns,
+ *     host memory, async work pending on the ctx, an info whose rows leave window->n_rows, whose
+ *     row_off decreases or whose rows overlap the record before;
+ *   when cap_rows is smaller than the kept rows of [0, n_done): n_rows holds the need (n_dropped,
+ *     n_done, n_miss, rec_off and miss_row are written as on success) and no row is written.
+ *     cap_rows >= window->n_rows always suffices.
+ * Whatever the outcome, nothing is written outside [0, cap_rows) of each row array,
+ * rec_off[0 .. n_recs] and miss_row[0 .. cap_miss). n_recs == 0 or no rows gives all zeros and
+ * n_done = n_recs. Synchronous, one read-back of a small head on the common path. */
+#define NXG_REPLAY_DROP  0xffffffffffffffffull  /* no path, or the session's filter does not match it */
+#define NXG_REPLAY_MISS  0xfffffffffffffffeull  /* has a path the filter matches, not yet published */
+typedef struct NxgReplayTable {      /* `published`, session_shard.rs:42, with the host's filter folded in */
+    uint64_t n_ids;                  /* pub_id_of_arch covers archive Ids [0, n_ids) */
+    const uint64_t* pub_id_of_arch;  /* device: the publisher Id, NXG_REPLAY_DROP or NXG_REPLAY_MISS */
+} NxgReplayTable;
+typedef struct NxgReplayRows {       /* caller's device arrays, cap_rows entries each */
+    uint64_t cap_rows;
+    uint64_t* id; uint8_t* tag; uint64_t* fixed; uint32_t* aux;
+    uint64_t* src_row;               /* the row's index in the window (or image) columns */
+    uint64_t* rec_off;               /* device [n_recs + 1]: record i's updates are rows [rec_off[i], rec_off[i+1]) */
+    uint64_t* miss_row; uint64_t cap_miss;    /* device: window rows of the stopping record that missed */
+    uint64_t n_rows, n_dropped, n_done, n_miss;   /* written by the call */
+} NxgReplayRows;
+bool nxg_replay_window(NxgCtx* ctx, const NxgColumns* window, const NxgArchiveBatchInfo* info,
+                       uint32_t n_recs, const NxgReplayTable* tab, NxgReplayRows* out,
+                       NetidxError* err);
+/* reimage (session_shard.rs:375-409, on every seek and at session start): every Id of the pathmap
+ * gets its image value, or Null when the image has none or has Unsubscribed. `image` is what
+ * nxg_archive_build_image produced (ids ascending; only id / tag / fixed / aux and n_rows are
+ * read); order[0 .. n_order) are the pathmap's archive Ids in iter_pathmap order, device memory,
+ * in any order, duplicates tolerated; `tab` as above. The output is one record (rec_off has 2
+ * entries, n_done == 1 always): for each order[j] that is kept, the row (pub id, the image's value,
+ * src_row = the image row); when the image has no row for the Id, or has Unsubscribed, the row is
+ * Null with src_row = UINT64_MAX. The Id is found by bisection over the image's sorted ids. Drops
+ * are counted. Nothing depends on a miss inside one reimage, so misses do not stop the call: every
+ * position j that missed is listed in miss_row, in order, and n_miss is exact even past cap_miss.
+ * Errors, bounds and synchrony as nxg_replay_window; cap_rows >= n_order always suffices. */
+bool nxg_replay_image(NxgCtx* ctx, const NxgArchiveImage* image, const uint32_t* order,
+                      uint64_t n_order, const NxgReplayTable* tab, NxgReplayRows* out,
+                      NetidxError* err);
+
 /* ---- the publisher <-> subscriber connection (BASELINE configs[0]) ------------------------
  * Replaces hello_publisher (netidx/src/subscriber/connection.rs:120-140), ClientCtx::hello
  * (publisher/server.rs:367-381), read_task / flush_buf (channel.rs:107-126, 379-443) and the

@@ -19,7 +19,8 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     PERM_WRITE, WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED,
                     WRITE_NOT_ACCEPTED, PathTable, SubscribeTable, SubscribeRoute, path_is_plain,
                     path_hash, NO_ID, SUB_PERM_DENY, PERM_ALL, SUB_SUBSCRIBED, SUB_NO_SUCH_VALUE, SUB_DENIED,
-                    SUB_DEFERRED, SUB_IGNORED, MAX_DEFERRED, ValueTable, ValueCapacity)
+                    SUB_DEFERRED, SUB_IGNORED, MAX_DEFERRED, ValueTable, ValueCapacity,
+                    ReplayRows, REPLAY_DROP, REPLAY_MISS)
 
 __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays", "lib",
            "frame_split", "frame_header", "frame_parse_header", "LAYOUT_F64", "LAYOUT_MIXED",
@@ -34,4 +35,5 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED", "PathTable",
            "SubscribeTable", "SubscribeRoute", "path_is_plain", "path_hash", "NO_ID", "SUB_PERM_DENY",
            "PERM_ALL", "SUB_SUBSCRIBED", "SUB_NO_SUCH_VALUE", "SUB_DENIED", "SUB_DEFERRED",
-           "SUB_IGNORED", "MAX_DEFERRED", "ValueTable", "ValueCapacity"]
+           "SUB_IGNORED", "MAX_DEFERRED", "ValueTable", "ValueCapacity",
+           "ReplayRows", "REPLAY_DROP", "REPLAY_MISS"]

@@ -258,6 +258,21 @@ class NxgArchiveImage(C.Structure):
                 ("n_rows", C.c_uint64), ("n_filtered", C.c_uint64)]
 
 
+class NxgReplayTable(C.Structure):
+    _fields_ = [("n_ids", C.c_uint64), ("pub_id_of_arch", C.c_void_p)]
+
+
+class NxgReplayRows(C.Structure):
+    _fields_ = [("cap_rows", C.c_uint64), ("id", C.c_void_p), ("tag", C.c_void_p),
+                ("fixed", C.c_void_p), ("aux", C.c_void_p), ("src_row", C.c_void_p),
+                ("rec_off", C.c_void_p), ("miss_row", C.c_void_p), ("cap_miss", C.c_uint64),
+                ("n_rows", C.c_uint64), ("n_dropped", C.c_uint64), ("n_done", C.c_uint64),
+                ("n_miss", C.c_uint64)]
+
+
+REPLAY_DROP, REPLAY_MISS = 0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFFE
+
+
 class NxgStatus(C.Structure):
     _fields_ = [
         ("n_rows", C.c_uint64), ("n_children", C.c_uint64), ("n_ctl", C.c_uint64),
@@ -419,6 +434,13 @@ SIGNATURES = {
     "nxg_archive_build_image": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_uint64,
                                            C.c_void_p, C.POINTER(NxgArchiveImage),
                                            C.POINTER(NetidxError)]),
+    "nxg_replay_window": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns),
+                                     C.POINTER(NxgArchiveBatchInfo), C.c_uint32,
+                                     C.POINTER(NxgReplayTable), C.POINTER(NxgReplayRows),
+                                     C.POINTER(NetidxError)]),
+    "nxg_replay_image": (C.c_bool, [C.c_void_p, C.POINTER(NxgArchiveImage), C.c_void_p,
+                                    C.c_uint64, C.POINTER(NxgReplayTable),
+                                    C.POINTER(NxgReplayRows), C.POINTER(NetidxError)]),
     "nxg_session_connect": (C.c_void_p, [C.c_char_p, C.c_uint16, C.POINTER(NetidxError)]),
     "nxg_session_listen": (C.c_void_p, [C.c_char_p, C.c_uint16, C.POINTER(C.c_uint16),
                                         C.POINTER(NetidxError)]),
@@ -660,6 +682,83 @@ class _ColumnsView:
     pass
 
 
+class ReplayRows:
+    """The update rows of a replayed window or image (nxg_replay_window / nxg_replay_image): id /
+    tag / fixed / aux / src_row tensors of n_rows rows, rec_off (n_recs + 1 entries: record i's
+    updates are rows [rec_off[i], rec_off[i+1])) and miss_row (cap_miss entries). n_done, n_dropped
+    and n_miss as the call wrote them. The rows borrow the window: children and text stay where the
+    window decode put them. `arrays`: caller-made tensors to write into instead (any of the seven
+    names; cap_rows / cap_miss then state what the call may write)."""
+
+    ROW_ARRAYS = (("id", "int64"), ("tag", "uint8"), ("fixed", "int64"), ("aux", "int32"),
+                  ("src_row", "int64"))
+
+    def __init__(self, cap_rows, n_recs, cap_miss=0, device="cuda", arrays=None):
+        import torch
+        arrays = arrays or {}
+        for k, dt in self.ROW_ARRAYS:
+            setattr(self, k, arrays[k] if k in arrays else torch.zeros(
+                max(cap_rows, 1), dtype=getattr(torch, dt), device=device))
+        self.rec_off = arrays["rec_off"] if "rec_off" in arrays else torch.zeros(
+            n_recs + 1, dtype=torch.int64, device=device)
+        self.miss_row = arrays["miss_row"] if "miss_row" in arrays else torch.zeros(
+            max(cap_miss, 1), dtype=torch.int64, device=device)
+        torch.cuda.synchronize(device)  # (as Columns: the zero fill is done)
+        self.n_recs = n_recs
+        self.s = NxgReplayRows()
+        self.s.cap_rows, self.s.cap_miss = cap_rows, cap_miss
+        for k in ("id", "tag", "fixed", "aux", "src_row", "rec_off", "miss_row"):
+            setattr(self.s, k, getattr(self, k).data_ptr())
+        self._off = None
+
+    n_rows = property(lambda self: self.s.n_rows)
+    n_dropped = property(lambda self: self.s.n_dropped)
+    n_done = property(lambda self: self.s.n_done)
+    n_miss = property(lambda self: self.s.n_miss)
+
+    def offsets(self):
+        """rec_off on the host (uint64), read once per call."""
+        if self._off is None:
+            self._off = self.rec_off[:self.n_recs + 1].cpu().numpy().view(np.uint64)
+        return self._off
+
+    def misses(self):
+        """The listed miss rows on the host (uint64): min(n_miss, cap_miss) of them."""
+        n = min(self.s.n_miss, self.s.cap_miss)
+        return self.miss_row[:n].cpu().numpy().view(np.uint64)
+
+    def numpy(self):
+        n = self.s.n_rows
+        u = {"int64": np.uint64, "uint8": np.uint8, "int32": np.uint32}
+        return {k: getattr(self, k)[:n].cpu().numpy().view(u[dt]) for k, dt in self.ROW_ARRAYS}
+
+    def _view(self, window_cols, lo, hi):
+        v = _ColumnsView()
+        v.keep = (self, window_cols)
+        v.s = NxgColumns()
+        C.memmove(C.byref(v.s), C.byref(window_cols.s), C.sizeof(NxgColumns))
+        v.s.cap_rows = v.s.n_rows = hi - lo
+        v.s.n_ctl = 0
+        for k in ("id", "tag", "fixed", "aux"):
+            t = getattr(self, k)[lo:hi]
+            setattr(v, k, t)
+            setattr(v.s, k, t.data_ptr() if hi > lo else getattr(self, k).data_ptr())
+        v.src_row = self.src_row[lo:hi]
+        return v
+
+    def columns(self, window_cols):
+        """Rows [0, n_rows) as the Columns view publish_commit, encode_clients and
+        ValueTable.apply take (heap = the window's buffer): the row arrays with the window's child
+        arrays (a view; both must stay alive)."""
+        return self._view(window_cols, 0, int(self.s.n_rows))
+
+    def record(self, i, window_cols):
+        """Record i's updates as such a view (Speed::Limited: one commit per record): the same
+        arrays at offset rec_off[i]."""
+        off = self.offsets()
+        return self._view(window_cols, int(off[i]), int(off[i + 1]))
+
+
 class WriteCols:
     """The two further fields of To::Write rows (NxgWriteCols): wflags (WRITE_REPLY |
     WRITE_NO_WID) and wid (the WriteId) per row. torch tensors on `device` (pinned host memory
@@ -837,6 +936,55 @@ class Codec:
         _check(lib().nxg_archive_build_image(self.ctx, C.byref(cols.s), n_ids, _ptr(keep),
                                              C.byref(img.s), C.byref(err)), err)
         return img
+
+    @staticmethod
+    def _replay_finish(ok, err, out):
+        out._off = None
+        if not ok:
+            msg = err.msg.decode() if err.msg else "unknown error"
+            lib().nxg_error_free(C.byref(err))
+            e = CodecError(msg)
+            e.rows = out  # (a capacity short: n_rows holds the need)
+            raise e
+        return out
+
+    def replay_window(self, cols, infos, table, out=None, cap_miss=64):
+        """A decoded window as publisher update rows (nxg_replay_window; process_batch,
+        session_shard.rs:196-245). cols / infos: archive_decode_window's columns and per-record
+        infos (or (row_off, n_rows) pairs; a tail infos[k:] replays from record k); table: the
+        device int64 tensor pub_id_of_arch (the publisher Id, REPLAY_DROP or REPLAY_MISS per
+        archive Id). Returns a ReplayRows (`out`, or a new one of the window's rows): stopped in
+        front of record n_done < len(infos) when that record holds Ids to publish first (misses()).
+        A CodecError raised here carries the ReplayRows as `.rows`."""
+        n = len(infos)
+        info = (NxgArchiveBatchInfo * max(n, 1))()
+        for i, t in enumerate(infos):
+            if isinstance(t, NxgArchiveBatchInfo):
+                info[i].row_off, info[i].n_rows = t.row_off, t.n_rows
+            else:
+                info[i].row_off, info[i].n_rows = t[0], t[1]
+        if out is None:
+            out = ReplayRows(int(cols.s.n_rows), n, cap_miss, cols.id.device)
+        tab = NxgReplayTable(table.numel(), table.data_ptr() if table.numel() else None)
+        err = NetidxError()
+        ok = lib().nxg_replay_window(self.ctx, C.byref(cols.s), info, n, C.byref(tab),
+                                     C.byref(out.s), C.byref(err))
+        return self._replay_finish(ok, err, out)
+
+    def replay_image(self, image, order, table, out=None, cap_miss=64):
+        """reimage (session_shard.rs:375-409) as publisher update rows (nxg_replay_image): image:
+        archive_build_image's; order: the pathmap's archive Ids, a device int32 tensor (uint32
+        storage); table as for replay_window. Returns a ReplayRows of one record; misses() lists
+        the positions of `order` whose Ids are to be published first (they do not stop the call)."""
+        n = order.numel()
+        if out is None:
+            out = ReplayRows(n, 1, cap_miss, order.device)
+        tab = NxgReplayTable(table.numel(), table.data_ptr() if table.numel() else None)
+        err = NetidxError()
+        ok = lib().nxg_replay_image(self.ctx, C.byref(image.s),
+                                    C.c_void_p(order.data_ptr() if n else None), n,
+                                    C.byref(tab), C.byref(out.s), C.byref(err))
+        return self._replay_finish(ok, err, out)
 
     def archive_compress(self, src, records, indexed=False, zdict=None, literals=0):
         """Uncompressed archive records (host bytes `src`, [(off, len)] after each RecordHeader)

@@ -19,6 +19,7 @@
 #include "nxg_internal.h"
 #include "nxg_path_hash.h"
 #include "nxg_record.h"
+#include "nxg_replay.h"
 
 namespace {
 
@@ -2808,6 +2809,163 @@ bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
         return false;
     }
     return true;
+}
+
+// ---- playback: a decoded window (process_batch, session_shard.rs:196-245) or its image (reimage,
+// session_shard.rs:375-409) as publisher update rows (nxg_replay.hip). Argument checks on the host,
+// the launches, one read-back of the call's head; a second small launch and read-back only when a
+// record missed.
+static bool replay_out_ok(const NxgReplayRows* out, const char* what, NetidxError* err) {
+    if (!out->rec_off || (out->cap_miss && !out->miss_row) ||
+        (out->cap_rows && (!out->id || !out->tag || !out->fixed || !out->aux || !out->src_row))) {
+        set_err(err, "null output array");
+        return false;
+    }
+    const void* need[] = {out->rec_off, out->cap_miss ? out->miss_row : nullptr,
+                          out->cap_rows ? out->id : nullptr, out->cap_rows ? out->tag : nullptr,
+                          out->cap_rows ? out->fixed : nullptr, out->cap_rows ? out->aux : nullptr,
+                          out->cap_rows ? out->src_row : nullptr};
+    for (const void* p : need)
+        if (p && !is_device_ptr(p)) {
+            set_err(err, "%s takes device memory only (the table, the columns and every output "
+                         "array)", what);
+            return false;
+        }
+    return true;
+}
+
+// the launches and the read-backs; a.n > 0
+static bool replay_run(NxgCtx* c, NxgRpArgs a, const std::vector<uint64_t>& hbeg,
+                const std::vector<uint64_t>& hend, NxgReplayRows* out, NetidxError* err) {
+    a.cap_rows = out->cap_rows;
+    a.oid = out->id, a.otag = out->tag, a.ofixed = out->fixed, a.oaux = out->aux;
+    a.osrc = out->src_row;
+    a.rec_off = out->rec_off;
+    a.miss_row = out->miss_row;
+    a.cap_miss = out->cap_miss;
+    if (!ensure_dscratch(c, nxg_rp_scratch_bytes(a.n, a.n_recs), err)) return false;
+    NxgRpHead h;
+    HIPCHK(nxg_launch_replay(a, c->dscratch, hbeg.data(), hend.data(), c->stream));
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.stop_inv) {  // rare: list the misses of the stopping record
+        HIPCHK(nxg_launch_replay_misses(a, c->dscratch, a.order ? 0u : (uint32_t)h.n_done,
+                                        c->stream));
+        HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    out->n_rows = h.n_rows;
+    out->n_done = h.n_done;
+    out->n_miss = h.n_miss;
+    // records in front of n_done hold no miss: what is not kept there was dropped
+    uint64_t rows = 0;
+    for (uint64_t i = 0; i < h.n_done && i < a.n_recs; i++) rows += hend[i] - hbeg[i];
+    out->n_dropped = rows - h.n_rows - (a.order ? h.n_miss : 0);
+    if (h.n_rows > out->cap_rows) {
+        set_err(err, "the rows' capacity is %llu; the replay keeps %llu",
+                (unsigned long long)out->cap_rows, (unsigned long long)h.n_rows);
+        return false;
+    }
+    return true;
+}
+
+bool nxg_replay_window(NxgCtx* c, const NxgColumns* window, const NxgArchiveBatchInfo* info,
+                       uint32_t n_recs, const NxgReplayTable* tab, NxgReplayRows* out,
+                       NetidxError* err) {
+    if (!c || !window || !tab || !out || (n_recs && !info) || (tab->n_ids && !tab->pub_id_of_arch)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (window->mem != NXG_MEM_DEVICE || window->layout != NXG_LAYOUT_MIXED ||
+        (window->n_rows && (!window->id || !window->tag || !window->fixed || !window->aux))) {
+        set_err(err, "a window is replayed from device MIXED-layout columns");
+        return false;
+    }
+    std::vector<uint64_t> hbeg((size_t)n_recs + 1), hend(n_recs);
+    for (uint32_t i = 0; i < n_recs; i++) {
+        const uint64_t lo = info[i].row_off, cnt = info[i].n_rows;
+        if (lo > window->n_rows || cnt > window->n_rows - lo) {
+            set_err(err, "info[%u]: rows [%llu, + %llu) leave the window's %llu rows", i,
+                    (unsigned long long)lo, (unsigned long long)cnt,
+                    (unsigned long long)window->n_rows);
+            return false;
+        }
+        if (i && lo < hend[i - 1]) {
+            set_err(err, "info[%u].row_off (%llu) lies in front of the end of record %u (%llu): "
+                         "row_off must not decrease and records must not overlap", i,
+                    (unsigned long long)lo, i - 1, (unsigned long long)hend[i - 1]);
+            return false;
+        }
+        hbeg[i] = lo;
+        hend[i] = lo + cnt;
+    }
+    const uint64_t first = n_recs ? hbeg[0] : 0, n = n_recs ? hend[n_recs - 1] - first : 0;
+    hbeg[n_recs] = first + n;
+    if (!no_pending(c, err)) return false;
+    if (!set_device(c, err)) return false;
+    if (!replay_out_ok(out, "nxg_replay_window", err)) return false;
+    if ((n && !is_device_ptr(window->id)) || (tab->n_ids && !is_device_ptr(tab->pub_id_of_arch))) {
+        set_err(err, "nxg_replay_window takes device memory only (the table, the columns and every "
+                     "output array)");
+        return false;
+    }
+    out->n_rows = out->n_dropped = out->n_miss = 0;
+    out->n_done = n_recs;
+    if (n == 0) {  // no rows: no update, and no kernel runs
+        HIPCHK(hipMemsetAsync(out->rec_off, 0, ((uint64_t)n_recs + 1) * 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    NxgRpArgs a{};
+    a.id = window->id;
+    a.tag = window->tag, a.fixed = window->fixed, a.aux = window->aux;
+    a.first = first, a.n = n;
+    a.n_recs = n_recs;
+    a.pub_id_of_arch = tab->pub_id_of_arch;
+    a.n_ids = tab->n_ids;
+    return replay_run(c, a, hbeg, hend, out, err);
+}
+
+bool nxg_replay_image(NxgCtx* c, const NxgArchiveImage* image, const uint32_t* order,
+                      uint64_t n_order, const NxgReplayTable* tab, NxgReplayRows* out,
+                      NetidxError* err) {
+    if (!c || !image || !tab || !out || (n_order && !order) ||
+        (tab->n_ids && !tab->pub_id_of_arch)) {
+        set_err(err, "null argument");
+        return false;
+    }
+    if (image->n_rows > image->cap_rows ||
+        (image->n_rows && (!image->id || !image->tag || !image->fixed || !image->aux))) {
+        set_err(err, "the image's arrays are null or n_rows exceeds cap_rows");
+        return false;
+    }
+    if (!no_pending(c, err)) return false;
+    if (!set_device(c, err)) return false;
+    if (!replay_out_ok(out, "nxg_replay_image", err)) return false;
+    if ((n_order && !is_device_ptr(order)) || (image->n_rows && !is_device_ptr(image->id)) ||
+        (tab->n_ids && !is_device_ptr(tab->pub_id_of_arch))) {
+        set_err(err, "nxg_replay_image takes device memory only (the image, order, the table and "
+                     "every output array)");
+        return false;
+    }
+    out->n_rows = out->n_dropped = out->n_miss = 0;
+    out->n_done = 1;
+    if (n_order == 0) {
+        HIPCHK(hipMemsetAsync(out->rec_off, 0, 2 * 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    NxgRpArgs a{};
+    a.order = order;
+    a.img_id = image->id;
+    a.n_img = image->n_rows;
+    a.tag = image->tag, a.fixed = image->fixed, a.aux = image->aux;
+    a.first = 0, a.n = n_order;
+    a.n_recs = 1;
+    a.pub_id_of_arch = tab->pub_id_of_arch;
+    a.n_ids = tab->n_ids;
+    const std::vector<uint64_t> hbeg{0, n_order}, hend{n_order};
+    return replay_run(c, a, hbeg, hend, out, err);
 }
 
 // ---- the value table: `pbl.current = v` and a subscription's `last`, on the device --------------
