@@ -88,7 +88,7 @@ struct ColsDesc;
 // Every launcher takes the call's status slot `st` and `zst`, the slot that the call 512 calls
 // later will use (nxg_take_zero_slot()). Block 0 of the kernel that receives it zeroes `zst` on
 // entry, so the ring needs no per-call memset; a call that launches no such kernel (an empty
-// frame or batch) has the host zero it instead (nxg_zero_used, nxg_api.cpp).
+// frame or batch) has the host zero it instead (nxg_zero_used, nxg_ctx.cpp).
 __device__ inline void zero_status(DevStatus* zst) {
     if (zst && blockIdx.x == 0 && threadIdx.x == 0) *zst = DevStatus{};
 }

@@ -15,26 +15,16 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "../../include/nxg_codec.h"
+#include "nxg_host.h"  // set_err and HIPCHK; the codec is used through the public ABI only
+
+using nxg_host::set_err;
 
 namespace {
-
-void set_err(NetidxError* err, const char* fmt, ...) {
-    if (!err) return;
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    free(err->msg);
-    err->msg = strdup(buf);
-}
 
 struct Rccl {
     void* h = nullptr;
@@ -100,14 +90,6 @@ struct NxgComm {
         ncclResult_t r_ = (expr);                                                             \
         if (r_ != ncclSuccess) {                                                              \
             set_err(err, "%s failed: %s", #expr, comm->r->GetErrorString(r_));                \
-            return false;                                                                     \
-        }                                                                                     \
-    } while (0)
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            set_err(err, "%s failed: %s", #expr, hipGetErrorString(e_));                      \
             return false;                                                                     \
         }                                                                                     \
     } while (0)

@@ -1,5 +1,5 @@
 // nxg_path_hash.h -- the path table's hash, shared by the kernels of nxg_route_subscribes.hip
-// (which read a path eight bytes at a time) and the host's nxg_path_hash (nxg_api.cpp).
+// (which read a path eight bytes at a time) and the host's nxg_path_hash (nxg_api_route.cpp).
 //
 // A path of len bytes is hashed over its little-endian 8-byte words w_0, w_1, ... (the last one
 // zero above the path's end): h = kSeed ^ len; h = mix(h, w_i) for each word; finish_hash(h).

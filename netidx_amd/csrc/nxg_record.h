@@ -1,5 +1,5 @@
 // nxg_record.h -- nxg_record_entries: what its kernels (nxg_record.hip) and the host call
-// (nxg_api.cpp) share. Not ABI.
+// (nxg_api_archive.cpp) share. Not ABI.
 #pragma once
 #include "nxg_internal.h"
 

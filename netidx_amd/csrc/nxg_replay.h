@@ -1,5 +1,5 @@
 // nxg_replay.h -- nxg_replay_window / nxg_replay_image: what their kernels (nxg_replay.hip) and
-// the host calls (nxg_api.cpp) share. Not ABI.
+// the host calls (nxg_api_archive.cpp) share. Not ABI.
 #pragma once
 #include "nxg_internal.h"
 

@@ -251,7 +251,7 @@ LDS_PER_CU = 160 * 1024
 
 
 def assert_more_tiles_than_workgroups(tiles, staging):
-    """The persistent grid is CUs * (workgroups per CU - 1) (nxg_api.cpp). A workgroup's LDS is
+    """The persistent grid is CUs * (workgroups per CU - 1) (nxg_ctx.cpp). A workgroup's LDS is
     more than its staging, so LDS alone bounds the workgroups per CU, whatever the occupancy
     query answers: with fewer workgroups than tiles some of them loop and reuse their staging.
     How many take a second tile is not known here (MI355X, 256 CUs: at most 1024 workgroups for
