@@ -1127,6 +1127,91 @@ bool nxg_record_entries(NxgCtx* ctx, const NxgColumns* batch, const uint8_t* hea
                         const NxgDispatch* d, uint32_t n_chans, const NxgRecordTable* tab,
                         NxgRecordBatches* out, NetidxError* err);
 
+/* ---- indexed archives: the RecordIndex in front of every batch (netidx-archive/src/logfile/
+ * mod.rs:146-149, #[derive(Pack)] struct RecordIndex { index: Vec<Id> }).
+ *
+ * nxg_archive_index_records replaces the HashSet loop of add_batch (writer.rs:407-429): the indexes
+ * of n_recs records in one call. `key` (device, n_keys positions) and `seg_off` (device, n_recs + 1
+ * entries, in the form of NxgDispatch.chan_off) give record c the positions [seg_off[c],
+ * seg_off[c+1]); positions in front of seg_off[0] or behind seg_off[n_recs] belong to no record and
+ * are not read. n_keys is stated so that no launch depends on a read-back.
+ *   tab == NULL: key[p] is the archive Id itself (the id column given to nxg_encode_archive_batch,
+ *     or a decoded window's). An Id >= 2^32 is refused; the message names the lowest such position,
+ *     whatever the scheduling.
+ *   tab != NULL: key[p] is a SubId, translated and filtered exactly as nxg_record_entries does: kept
+ *     iff key[p] < tab->n_subs and arch_id_of_sub[key[p]] != NXG_NO_SLOT. Called with d->ent_sub,
+ *     d->chan_off, d->n_entries and the recorder's table, the call yields the index of exactly the
+ *     record nxg_record_entries wrote for each channel; the file's record is index[c] | batch[c].
+ * Record c's index is  varint(L) varint(count) varint(id)...  where `inner` is the bytes from the
+ * count on and L = inner + varint_len(inner + varint_len(inner)) (len_wrapped_len, pack.rs:522-525):
+ * its distinct kept Ids, each once, in order of first occurrence. (The reference drains a
+ * FxHashSet, whose order nobody can pin; the reader is order-blind.) A record with no kept position
+ * gets no bytes, as add_batch writes nothing for an empty batch (writer.rs:405): idx_off[c] ==
+ * idx_off[c+1], idx_ids[c] == 0. Indexes lie back to back in record order: idx_off[0] == 0,
+ * idx_off[n_recs] == n_bytes. The index of an *image* record is the constant 02 00 (writer.rs:408
+ * inserts nothing): the host writes those two bytes itself, this call is for delta records.
+ * false with a message:
+ *   on misuse, before any launch (a null argument, host memory, more than 2^28 positions, async
+ *     work pending on the ctx);
+ *   when seg_off decreases (the message names the lowest record c with seg_off[c+1] < seg_off[c])
+ *     or ends behind n_keys (the last record);
+ *   for an Id >= 2^32 (tab == NULL);
+ *   when idx_ids[c] * 4 exceeds MAX_VEC (PackError::TooBig, pack.rs:943; the first such record);
+ *   when n_bytes > cap_bytes: n_bytes, n_ids_total, idx_off and idx_ids then hold the true values.
+ * Every check and every size is settled before the first byte of `out` is written: after any false
+ * return no byte of `out` has changed. Whatever the outcome, nothing outside [out, out +
+ * cap_bytes), idx_off[0 .. n_recs] and idx_ids[0 .. n_recs) is written. n_recs == 0 or n_keys == 0
+ * gives all zeros and launches nothing: with no keys seg_off is not examined (its entries are not
+ * read, so one that would end behind n_keys is not refused). Synchronous, one read-back of a small
+ * head; out NULL sizes only.
+ * Memory: the context keeps a table of 12 bytes per slot, a power of two >= 2 * n_keys slots (384
+ * MiB at 10^7 positions, 6 GiB at the limit of 2^28), and 9 bytes per position of scratch. Both
+ * are grown on demand and stay with the context at the size of its largest call until
+ * nxg_ctx_destroy; a caller that cannot afford that splits its records over several calls. */
+typedef struct NxgArchiveIndexes {
+    uint64_t cap_bytes;  /* capacity of out */
+    uint8_t* out;        /* device; NULL: size only */
+    uint64_t* idx_off;   /* device [n_recs + 1]: record c's RecordIndex is out[idx_off[c], idx_off[c+1]) */
+    uint64_t* idx_ids;   /* device [n_recs]: distinct Ids in record c's index */
+    uint64_t n_bytes, n_ids_total;   /* written by the call */
+} NxgArchiveIndexes;
+bool nxg_archive_index_records(NxgCtx* ctx, const uint64_t* key, uint64_t n_keys,
+                               const uint64_t* seg_off, uint32_t n_recs,
+                               const NxgRecordTable* tab /* may be NULL */, NxgArchiveIndexes* out,
+                               NetidxError* err);
+
+/* nxg_archive_scan_index replaces scan_index_at (reader.rs:394-422), the test matching_idxs
+ * (reader.rs:559-581) makes of every record of a filtered read: n records in one call. dbuf is
+ * device memory of buf_len bytes; record i's RecordIndex starts at dbuf + idx_off[i] (past the
+ * RecordHeader, and past the u32 of a compressed record) and its record ends at idx_end[i]
+ * (idx_off, idx_end and verdict are host memory). keep[a] != 0 iff archive Id a is in the filter
+ * set: the array nxg_archive_build_image takes (device, n_ids bytes).
+ * verdict[i] is scan_index_at, statement by statement:
+ *   index_len = decode_varint; a failure is NXG_INDEX_ERR_SHORT or NXG_INDEX_ERR_FORMAT.
+ *   The body is the index_len - varint_len(index_len) bytes behind the bytes that varint consumed
+ *   (a non-canonical 81 00 consumes two), clipped at idx_end[i] (Buf::take clips, it does not fail).
+ *   The body is walked varint by varint; the Vec's count is one of them, because the reference does
+ *   not skip it: a record whose count equals a kept Id matches, and 02 00 matches iff keep[0].
+ *   Each value is truncated to u32 (Id(id as u32): the varint of 2^32 + 5 tests keep[5]); it hits
+ *   when it is < n_ids and kept. The first hit ends the walk with NXG_INDEX_MATCH, so errors behind
+ *   a hit are never seen; otherwise the first failing varint gives the verdict, NXG_INDEX_ERR_FORMAT
+ *   for ten continuation bytes inside the body, NXG_INDEX_ERR_SHORT when the body ends inside a
+ *   varint; otherwise NXG_INDEX_NONE.
+ * The reference logs an error and skips the record; whether to skip stays the caller's decision.
+ * Deviations: index_len == 0 underflows in the reference, here it is NXG_INDEX_ERR_FORMAT; the
+ * reference's slice runs to the end of the mmap, ours to the record's end.
+ * *n_match (may be NULL) counts the NXG_INDEX_MATCH verdicts. One launch covers all records, one
+ * pinned copy up, one read-back; n == 0 launches nothing. false on misuse: a null argument, a host
+ * dbuf or keep, idx_off[i] > idx_end[i], idx_end[i] > buf_len, async work pending on the ctx. */
+#define NXG_INDEX_NONE 0
+#define NXG_INDEX_MATCH 1
+#define NXG_INDEX_ERR_SHORT 2    /* PackError::BufferShort */
+#define NXG_INDEX_ERR_FORMAT 3   /* PackError::InvalidFormat */
+bool nxg_archive_scan_index(NxgCtx* ctx, const uint8_t* dbuf, uint64_t buf_len,
+                            const uint64_t* idx_off, const uint64_t* idx_end /* host [n] each */,
+                            uint32_t n, const uint8_t* keep /* device [n_ids] */, uint64_t n_ids,
+                            uint8_t* verdict /* host [n] */, uint64_t* n_match, NetidxError* err);
+
 /* ---- compressed archive batches: replaces the compressed branch of ArchiveReader::get_batch_at
  * (netidx-archive/src/logfile/reader.rs:453-477): a record after its RecordHeader is
  * u32 BE uncompressed record length | the RecordIndex (indexed files: a varint that is its own

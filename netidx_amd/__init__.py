@@ -14,7 +14,8 @@ from .codec import (BUFFER_SHORT, CAPACITY, DEPTH, HINT_MIXED, INVALID_FORMAT, L
                     msg_subscribe, msg_subscribed, msg_heartbeat, msg_parse, msg_update,
                     TAG_UNSUBSCRIBED, Resolver, ResolverClient, TagView, TAG_BINS, WriteCols,
                     NxgWriteCols, WRITE_REPLY, WRITE_NO_WID, PATH_WRITES, PATH_WRITES_FAST,
-                    NxgWriteDecodeOpts, ArchiveImage,
+                    NxgWriteDecodeOpts, ArchiveImage, INDEX_NONE, INDEX_MATCH, INDEX_ERR_SHORT,
+                    INDEX_ERR_FORMAT,
                     WindowCapacity, WriteTable, WriteRoute, RouteCapacity, NOT_SUBSCRIBED,
                     PERM_WRITE, WRITE_ROUTED, WRITE_UNSUBSCRIBED, WRITE_DENIED,
                     WRITE_NOT_ACCEPTED, PathTable, SubscribeTable, SubscribeRoute, path_is_plain,
@@ -30,7 +31,7 @@ __all__ = ["Codec", "Columns", "PackError", "CodecError", "columns_from_arrays",
            "Comm", "NxgRange", "range_link", "Session", "msg_subscribe", "msg_subscribed",
            "msg_heartbeat", "msg_parse", "msg_update", "TAG_UNSUBSCRIBED", "Resolver",
            "ResolverClient", "TagView", "TAG_BINS", "WriteCols", "NxgWriteCols", "WRITE_REPLY",
-           "WRITE_NO_WID", "PATH_WRITES", "PATH_WRITES_FAST", "NxgWriteDecodeOpts", "ArchiveImage", "WindowCapacity", "WriteTable",
+           "WRITE_NO_WID", "PATH_WRITES", "PATH_WRITES_FAST", "NxgWriteDecodeOpts", "ArchiveImage", "INDEX_NONE", "INDEX_MATCH", "INDEX_ERR_SHORT", "INDEX_ERR_FORMAT", "WindowCapacity", "WriteTable",
            "WriteRoute", "RouteCapacity", "NOT_SUBSCRIBED", "PERM_WRITE", "WRITE_ROUTED",
            "WRITE_UNSUBSCRIBED", "WRITE_DENIED", "WRITE_NOT_ACCEPTED", "PathTable",
            "SubscribeTable", "SubscribeRoute", "path_is_plain", "path_hash", "NO_ID", "SUB_PERM_DENY",

@@ -122,6 +122,14 @@ class NxgRecordBatches(C.Structure):
                 ("n_dropped", C.c_uint64)]
 
 
+class NxgArchiveIndexes(C.Structure):
+    _fields_ = [("cap_bytes", C.c_uint64), ("out", C.c_void_p), ("idx_off", C.c_void_p),
+                ("idx_ids", C.c_void_p), ("n_bytes", C.c_uint64), ("n_ids_total", C.c_uint64)]
+
+
+INDEX_NONE, INDEX_MATCH, INDEX_ERR_SHORT, INDEX_ERR_FORMAT = 0, 1, 2, 3
+
+
 class NxgWriteTable(C.Structure):
     _fields_ = [("n_ids", C.c_uint64), ("perm_of_id", C.c_void_p), ("slot_of_id", C.c_void_p),
                 ("n_slots", C.c_uint64), ("slot_chan_off", C.c_void_p), ("chan", C.c_void_p),
@@ -386,6 +394,14 @@ SIGNATURES = {
                                       C.POINTER(NxgDispatch), C.c_uint32,
                                       C.POINTER(NxgRecordTable), C.POINTER(NxgRecordBatches),
                                       C.POINTER(NetidxError)]),
+    "nxg_archive_index_records": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_uint32, C.POINTER(NxgRecordTable),
+                                             C.POINTER(NxgArchiveIndexes),
+                                             C.POINTER(NetidxError)]),
+    "nxg_archive_scan_index": (C.c_bool, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
+                                          C.c_void_p, C.POINTER(C.c_uint64),
+                                          C.POINTER(NetidxError)]),
     "nxg_encode_clients": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
                                       C.POINTER(NxgDispatch), C.c_uint32,
                                       C.POINTER(NxgClientFrames), C.POINTER(NetidxError)]),
@@ -1259,6 +1275,73 @@ class Codec:
         n, off, items, _, dropped = self.record_entries_into(batch, dispatch, table, heap,
                                                              out.data_ptr(), cap, off, items)
         return out[:n], off, items, dropped
+
+    def index_records_into(self, key, seg_off, table, out_ptr, cap, idx_off=None, idx_ids=None,
+                           n_keys=None):
+        """nxg_archive_index_records into device memory at `out_ptr` (0 / None: size only): the
+        RecordIndex of every record of `seg_off` (int64 device tensor, n_recs + 1 entries) over
+        `key` (int64 device tensor; n_keys: how many of its positions there are, default all).
+        `table`: None (key holds archive Ids) or arch_id_of_sub, a uint32 (int32 storage) device
+        tensor (key holds SubIds). Returns (n_bytes, idx_off, idx_ids, n_ids_total); a CodecError
+        raised here carries n_bytes, idx_off and idx_ids."""
+        import torch
+        n_recs = seg_off.numel() - 1
+        dev = seg_off.device
+        if idx_off is None:
+            idx_off = torch.empty(n_recs + 1, dtype=torch.int64, device=dev)
+        if idx_ids is None:
+            idx_ids = torch.empty(max(n_recs, 1), dtype=torch.int64, device=dev)
+        t = None
+        if table is not None:
+            t = C.byref(NxgRecordTable(table.numel(), table.data_ptr() if table.numel() else None))
+        o = NxgArchiveIndexes(cap, out_ptr or None, idx_off.data_ptr(), idx_ids.data_ptr(), 0, 0)
+        nk = key.numel() if n_keys is None else n_keys
+        err = NetidxError()
+        try:
+            _check(lib().nxg_archive_index_records(self.ctx, key.data_ptr() if nk else None, nk,
+                                                   seg_off.data_ptr(), n_recs, t, C.byref(o),
+                                                   C.byref(err)), err)
+        except CodecError as e:
+            e.n_bytes, e.idx_off, e.idx_ids = int(o.n_bytes), idx_off, idx_ids
+            raise
+        return int(o.n_bytes), idx_off, idx_ids[:n_recs], int(o.n_ids_total)
+
+    def index_records(self, key, seg_off, table=None, out=None):
+        """The RecordIndex of every record in one call (add_batch's HashSet loop, writer.rs:
+        407-429): record c's index is bytes[idx_off[c]:idx_off[c+1]], its distinct kept Ids in
+        order of first occurrence, idx_ids[c] of them. Returns (bytes, idx_off, idx_ids). `out`: a
+        uint8 device tensor to write into (all of it is the capacity); without one the call sizes
+        first and allocates."""
+        import torch
+        off = ids = None
+        if out is None:
+            n, off, ids, _ = self.index_records_into(key, seg_off, table, None, 0)
+            out = torch.empty(max(n, 16), dtype=torch.uint8, device=seg_off.device)
+            cap = n
+        else:
+            cap = out.numel()
+        n, off, ids, _ = self.index_records_into(key, seg_off, table, out.data_ptr(), cap, off, ids)
+        return out[:n], off, ids
+
+    def scan_index(self, dbuf, idx_off, idx_end, keep, buf_len=None):
+        """nxg_archive_scan_index (scan_index_at, reader.rs:394-422, for every record of a
+        filtered read): dbuf a uint8 device tensor, idx_off / idx_end host sequences (where each
+        record's RecordIndex starts and where the record ends), keep a uint8 device tensor indexed
+        by archive Id (or None: no Id is kept). Returns (verdict, n_match): a numpy uint8 array of
+        INDEX_NONE / INDEX_MATCH / INDEX_ERR_SHORT / INDEX_ERR_FORMAT."""
+        off = np.ascontiguousarray(idx_off, dtype=np.uint64)
+        end = np.ascontiguousarray(idx_end, dtype=np.uint64)
+        n = len(off)
+        assert len(end) == n
+        verdict = np.zeros(max(n, 1), np.uint8)
+        nm, err = C.c_uint64(0), NetidxError()
+        n_ids = keep.numel() if keep is not None else 0
+        _check(lib().nxg_archive_scan_index(
+            self.ctx, dbuf.data_ptr() if hasattr(dbuf, "data_ptr") else dbuf,
+            dbuf.numel() if buf_len is None else buf_len, off.ctypes.data, end.ctypes.data, n,
+            keep.data_ptr() if n_ids else None, n_ids, verdict.ctypes.data, C.byref(nm),
+            C.byref(err)), err)
+        return verdict[:n], nm.value
 
     def encoded_len(self, cols, heap=None):
         n, err = C.c_uint64(0), NetidxError()

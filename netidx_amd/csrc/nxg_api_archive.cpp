@@ -1,9 +1,10 @@
 // nxg_api_archive.cpp -- the archive calls of the C ABI (include/nxg_codec.h): archive batches,
 // zstd dictionaries, decompression and compression, a window of records and its image, recording
-// a dispatch's entries, replay.
+// a dispatch's entries, the RecordIndex of an indexed archive (written and scanned), replay.
 #include <mutex>
 
 #include "nxg_host.h"
+#include "nxg_archive_index.h"
 #include "nxg_record.h"
 #include "nxg_replay.h"
 
@@ -841,6 +842,144 @@ bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
                 (unsigned long long)h.n_bytes, (unsigned long long)out->cap_bytes);
         return false;
     }
+    return true;
+}
+
+// ---- the RecordIndex of an indexed archive (nxg_archive_index.hip): written per record
+// (add_batch, writer.rs:407-429) and scanned by Id set (scan_index_at, reader.rs:394-422).
+bool nxg_archive_index_records(NxgCtx* c, const uint64_t* key, uint64_t n_keys,
+                               const uint64_t* seg_off, uint32_t n_recs, const NxgRecordTable* tab,
+                               NxgArchiveIndexes* out, NetidxError* err) {
+    // (every argument is looked at before the ctx, so that each refusal is reached without one)
+    if (!seg_off) return refuse(err, "null argument (seg_off)");
+    if (!out) return refuse(err, "null argument (out)");
+    if (!out->idx_off) return refuse(err, "null argument (out->idx_off)");
+    if (n_recs && !out->idx_ids) return refuse(err, "null argument (out->idx_ids)");
+    if (n_keys && !key) return refuse(err, "null argument (key)");
+    if (tab && tab->n_subs && !tab->arch_id_of_sub)
+        return refuse(err, "null argument (tab->arch_id_of_sub)");
+    if (n_keys > kAixMaxKeys) {
+        set_err(err, "too many positions for one call (%llu)", (unsigned long long)n_keys);
+        return false;
+    }
+    if (!c) return refuse(err, "null argument (ctx)");
+    if (!all_device({seg_off, out->idx_off, n_recs ? out->idx_ids : nullptr, out->out,
+                     n_keys ? key : nullptr,
+                     tab && tab->n_subs ? tab->arch_id_of_sub : nullptr})) {
+        set_err(err, "nxg_archive_index_records takes device memory only (key, seg_off, "
+                     "tab->arch_id_of_sub, out->out, out->idx_off and out->idx_ids)");
+        return false;
+    }
+    if (!no_pending(c, err)) return false;
+    if (!set_device(c, err)) return false;
+    out->n_bytes = out->n_ids_total = 0;
+    if (n_keys == 0 || n_recs == 0) {  // no positions: no index, and no kernel runs
+        HIPCHK(hipMemsetAsync(out->idx_off, 0, ((uint64_t)n_recs + 1) * 8, c->stream));
+        if (n_recs) HIPCHK(hipMemsetAsync(out->idx_ids, 0, (uint64_t)n_recs * 8, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return true;
+    }
+    NxgAixArgs a{};
+    a.key = key;
+    a.seg_off = seg_off;
+    a.n_keys = n_keys;
+    a.n_recs = n_recs;
+    a.arch_id_of_sub = tab ? tab->arch_id_of_sub : nullptr;
+    a.n_subs = tab ? tab->n_subs : 0;
+    a.out = out->out;
+    a.cap = out->out ? out->cap_bytes : 0;
+    a.idx_off = out->idx_off;
+    a.idx_ids = out->idx_ids;
+    a.translate = tab != nullptr;  // (a table without entries drops every position)
+    if (!ensure_dscratch(c, nxg_aix_scratch_bytes(n_keys, n_recs), err) ||
+        !grow(c, c->aix_table, nxg_aix_table_bytes(nxg_aix_slot_bits(n_keys)), kGrowDouble, err))
+        return false;
+    NxgAixHead h;
+    HIPCHK(nxg_launch_aix_index(a, c->dscratch, c->aix_table, c->stream));
+    HIPCHK(hipMemcpyAsync(&h, c->dscratch, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h.seg_bad) {
+        set_err(err, "seg_off is not a list of records at record %u: it must not decrease and "
+                     "must not end behind n_keys (%llu)", h.seg_bad - 1,
+                (unsigned long long)n_keys);
+        return false;
+    }
+    if (h.wide_inv) {
+        const uint64_t p = ~h.wide_inv;
+        uint64_t v = 0;
+        HIPCHK(hipMemcpy(&v, key + p, 8, hipMemcpyDeviceToHost));
+        set_err(err, "position %llu: Id %llu is not below 2^32", (unsigned long long)p,
+                (unsigned long long)v);
+        return false;
+    }
+    if (h.vec_bad) {
+        set_err(err, "encode failed: record %u's Ids exceed MAX_VEC (PackError::TooBig)",
+                h.vec_bad - 1);
+        return false;
+    }
+    out->n_bytes = h.n_bytes;
+    out->n_ids_total = h.n_ids;
+    if (out->out && h.n_bytes > out->cap_bytes) {
+        set_err(err, "output buffer too small: need %llu bytes, have %llu",
+                (unsigned long long)h.n_bytes, (unsigned long long)out->cap_bytes);
+        return false;
+    }
+    return true;
+}
+
+bool nxg_archive_scan_index(NxgCtx* c, const uint8_t* dbuf, uint64_t buf_len,
+                            const uint64_t* idx_off, const uint64_t* idx_end, uint32_t n,
+                            const uint8_t* keep, uint64_t n_ids, uint8_t* verdict,
+                            uint64_t* n_match, NetidxError* err) {
+    if (n && !dbuf) return refuse(err, "null argument (dbuf)");
+    if (n && !idx_off) return refuse(err, "null argument (idx_off)");
+    if (n && !idx_end) return refuse(err, "null argument (idx_end)");
+    if (n && !verdict) return refuse(err, "null argument (verdict)");
+    if (n_ids && !keep) return refuse(err, "null argument (keep)");
+    for (uint32_t i = 0; i < n; i++)
+        if (idx_off[i] > idx_end[i] || idx_end[i] > buf_len) {
+            set_err(err, "record %u: [%llu, %llu) is not a range of the buffer's %llu bytes", i,
+                    (unsigned long long)idx_off[i], (unsigned long long)idx_end[i],
+                    (unsigned long long)buf_len);
+            return false;
+        }
+    if (!c) return refuse(err, "null argument (ctx)");
+    if (!no_pending(c, err)) return false;
+    if (!set_device(c, err)) return false;
+    if ((n && !is_device_ptr(dbuf)) || (n_ids && !is_device_ptr(keep))) {
+        set_err(err, "nxg_archive_scan_index takes a device buffer and a device keep array");
+        return false;
+    }
+    if (n_match) *n_match = 0;
+    if (n == 0) return true;
+    // one staging copy up: off[n], end[n], pbase[n + 1], res[n] (all ones)
+    const size_t words = 4 * (size_t)n + 1;
+    if (!grow(c, c->aix_dev, words * 8, kGrowDouble, err) ||
+        !grow(c, c->aix_host, words * 8, kGrowDouble, err))
+        return false;
+    uint64_t* h = reinterpret_cast<uint64_t*>(c->aix_host.get());
+    uint64_t* d = reinterpret_cast<uint64_t*>(c->aix_dev.get());
+    uint64_t pieces = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        h[i] = idx_off[i];
+        h[n + i] = idx_end[i];
+        h[2 * (size_t)n + i] = pieces;
+        pieces += nxg_aix_scan_pieces((uintptr_t)dbuf, idx_off[i], idx_end[i]);
+        h[3 * (size_t)n + 1 + i] = ~0ull;
+    }
+    h[3 * (size_t)n] = pieces;
+    HIPCHK(hipMemcpyAsync(d, h, words * 8, hipMemcpyHostToDevice, c->stream));
+    unsigned long long* res = reinterpret_cast<unsigned long long*>(d + 3 * (size_t)n + 1);
+    HIPCHK(nxg_launch_aix_scan(dbuf, d, d + n, d + 2 * (size_t)n, n, pieces, keep, n_ids, res,
+                               c->stream));
+    HIPCHK(hipMemcpyAsync(h, res, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    uint64_t m = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        verdict[i] = h[i] == ~0ull ? NXG_INDEX_NONE : (uint8_t)(h[i] & 3);
+        m += verdict[i] == NXG_INDEX_MATCH;
+    }
+    if (n_match) *n_match = m;
     return true;
 }
 

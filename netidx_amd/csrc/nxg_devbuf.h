@@ -26,7 +26,7 @@ struct GrowPolicy {
 };
 
 // One constant per row of the table in DESIGN.md ("Grow-on-demand buffers").
-constexpr GrowPolicy kGrowDouble{0, true, false, false};           // d/pscratch, aw_*, stage
+constexpr GrowPolicy kGrowDouble{0, true, false, false};           // d/pscratch, aw_*, aix_*, stage
 constexpr GrowPolicy kGrowDouble64K{1 << 16, true, false, false};  // rdesc, glws
 constexpr GrowPolicy kGrowTileStatus{4096, true, false, true};     // tstat (words)
 constexpr GrowPolicy kGrowEncScratch{1024, false, false, false};   // escratch (words)

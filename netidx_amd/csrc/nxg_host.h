@@ -4,7 +4,8 @@
 //
 //   nxg_ctx.cpp          contexts, columns, the status ring, host staging, debug entries, framing
 //   nxg_api.cpp          update decode / encode, the async backlog, nxg_ctx_sync, To batches
-//   nxg_api_archive.cpp  archive batches, zstd, windows and images, recording, replay
+//   nxg_api_archive.cpp  archive batches, zstd, windows and images, recording, the RecordIndex,
+//                        replay
 //   nxg_api_fanout.cpp   partition, dispatch, publish, per-client frames, the value table
 //   nxg_api_route.cpp    write / Subscribe / reply routing, the path table
 //   nxg_api_range.cpp    byte-range and share decode (multi-GPU)
@@ -164,6 +165,11 @@ struct NxgCtx {
     // or the image's table, and the pinned host mirror of head + records
     DevBuf<uint8_t> aw_dev;
     DevBuf<uint8_t, DevMem::Pinned> aw_host;
+    // the RecordIndex calls (nxg_archive_index.hip): the writer's (record, Id) table, cleared by a
+    // memset per call; the scan's offsets / result words and their pinned host mirror
+    DevBuf<uint8_t> aix_table;
+    DevBuf<uint8_t> aix_dev;
+    DevBuf<uint8_t, DevMem::Pinned> aix_host;
     uint64_t last_split = 0;  // last completed encode's DevStatus.split_start
 };
 
