@@ -1454,6 +1454,150 @@ bool nxg_replay_image(NxgCtx* ctx, const NxgArchiveImage* image, const uint32_t*
                       uint64_t n_order, const NxgReplayTable* tab, NxgReplayRows* out,
                       NetidxError* err);
 
+/* ---- oneshot queries: replaces do_oneshot's reply (netidx-archive/src/recorder/oneshot.rs:100-157,
+ * packed at oneshot.rs:194). OneshotReply(Vec<OneshotReplyShard>) and OneshotReplyShard { pathmap,
+ * image, deltas } are #[derive(Pack)] (recorder_client.rs:29-37), so both are length-wrapped
+ * (netidx-derive/src/lib.rs:113,137; len_wrapped_len, pack.rs:522-525):
+ *   reply   = varint(Lr) varint(n_shards) shard...
+ *   shard   = varint(Ls) pathmap image deltas
+ *   pathmap = varint(n) { varint(id) varint(len) path bytes }...    FxHashMap<Id, Path> (pack.rs:
+ *             1113-1124; Id: logfile/mod.rs:154-166; Path: path.rs:61-68 over ArcStr, pack.rs:444-455)
+ *   image   = varint(n) { varint(id) Event }...                     FxHashMap<Id, Event>
+ *   deltas  = varint(n) { i64 BE secs, u32 BE subsec nanos, varint(count) { varint(id) Event }... }...
+ *             VecDeque<(DateTime<Utc>, Vec<BatchItem>)> (pack.rs:1064-1074, 1416-1424, 1555-1567,
+ *             941-952)
+ * A HashMap has no order anybody can pin and the decoder inserts into a map, so every map is
+ * written in ascending Id order, as nxg_archive_build_image's image is. The image section is
+ * exactly what nxg_encode_archive_batch writes for the columns of nxg_archive_build_image(keep =
+ * sel).
+ *
+ * nxg_oneshot_pack_pathmap replaces oneshot.rs:111-120: the filter set and the pathmap section of
+ * one shard. `paths` is the shard's path index in Id order (pathindex.index().iter_pathmap()), keep
+ * is filter.is_match(path) per Id, computed by the host (glob matching stays there).
+ *   sel[a] = 1 iff keep[a] != 0 and Id a has a path (a non-empty range), else 0. It is the
+ *     reference's `filterset` and equally `pathmap.contains_key`: the `keep` array to hand to
+ *     nxg_archive_scan_index and nxg_archive_build_image.
+ *   out = varint(n_sel), then for every selected Id a in ascending order varint(a) varint(len) and
+ *     the len bytes path_bytes[path_off[a], path_off[a+1]).
+ * false with a message:
+ *   on misuse, before any launch (a null argument by name, host memory, more than 2^32 Ids, async
+ *     work pending on the ctx);
+ *   when path_off decreases (the message names the lowest Id a with path_off[a+1] < path_off[a],
+ *     whatever the scheduling);
+ *   when n_sel * 12 exceeds MAX_VEC (PackError::TooBig, pack.rs:1115: size_of::<Id>() +
+ *     size_of::<Path>(), an ArcStr being one pointer);
+ *   when n_bytes > cap_bytes. In the last two cases n_bytes and n_sel hold the true values.
+ * Every check and every size is settled before the first byte of `out` is written: after any false
+ * return no byte of `out` has changed (sel may have been written). Whatever the outcome, nothing
+ * outside [out, out + cap_bytes) and sel[0 .. n_ids) is written. n_ids == 0 gives the single byte
+ * 00 and launches nothing. Synchronous, one read-back of a small head; out NULL sizes only (sel is
+ * written all the same). */
+typedef struct NxgOneshotPaths {      /* pathindex.index().iter_pathmap(), oneshot.rs:113 */
+    uint64_t n_ids;                   /* archive Ids [0, n_ids) */
+    const uint64_t* path_off;         /* device [n_ids + 1], non-decreasing; Id a's path is path_bytes[path_off[a], path_off[a+1]) */
+    const uint8_t* path_bytes;        /* device, not NULL when n_ids > 0; an empty range: Id a has no path */
+} NxgOneshotPaths;
+typedef struct NxgOneshotPathmap {
+    uint64_t cap_bytes; uint8_t* out; /* device; NULL: size only */
+    uint8_t* sel;                     /* device [n_ids], written by the call: 1 iff keep[a] != 0 and a has a path */
+    uint64_t n_bytes, n_sel;          /* written by the call */
+} NxgOneshotPathmap;
+bool nxg_oneshot_pack_pathmap(NxgCtx* ctx, const NxgOneshotPaths* paths,
+                              const uint8_t* keep /* device [n_ids] */, NxgOneshotPathmap* out,
+                              NetidxError* err);
+
+/* nxg_oneshot_pack_deltas replaces oneshot.rs:146-149 for one window of read_deltas:
+ * batch.retain(|BatchItem(id, _)| pathmap.contains_key(id)), the drop of the records that end up
+ * empty, and the deltas elements of the records that remain. `window`, `info` and `dbuf` are what
+ * nxg_archive_decode_window produced and read (device MIXED columns; text at dbuf + fixed); only
+ * row_off and n_rows of info are read, and window rows outside the records belong to none: they
+ * are neither read, kept nor counted. ts_secs / ts_nanos are the DateTime<Utc> read_deltas pairs
+ * with each record (reader.rs:617-627), written verbatim as put_i64(secs) put_u32(nanos)
+ * (pack.rs:1555-1567): a leap second's nanos of 1 999 999 999 included, nothing is validated.
+ * `sel` is nxg_oneshot_pack_pathmap's (any keep array of that form).
+ *   Window row r of record i is kept iff window->id[r] < n_ids and sel[id] != 0. Any other row is
+ *   dropped and counted in n_dropped, and nothing else of it is read (a dropped row with a bad tag
+ *   is not an error): the rule nxg_record_entries has.
+ *   A record with a kept row becomes the element  secs nanos varint(rec_items[i]) item...,  each
+ *   item varint(id) Event, byte for byte what nxg_encode_archive_batch(..., heap = dbuf, ...) writes
+ *   for those rows. A record that keeps nothing gets no bytes (oneshot.rs:148): rec_off[i] ==
+ *   rec_off[i+1], rec_items[i] == 0, and it is not counted in n_kept_recs.
+ * Elements lie back to back in record order: rec_off[0] == 0, rec_off[n_recs] == n_bytes. The
+ * output is the deltas section without its leading count: the fragments of successive windows
+ * concatenate into one section (the reference's loop accumulates windows, oneshot.rs:139-156), and
+ * nxg_oneshot_shard_layout takes their summed n_bytes and n_kept_recs.
+ * false with a message:
+ *   on misuse, before any launch (a null argument by name, columns that are not device MIXED
+ *     columns, host memory, more than 2^32 Ids, 2^39 rows or more, async work pending on the ctx, an
+ *     info whose rows leave window->n_rows, whose row_off decreases or whose rows overlap the record
+ *     before, as nxg_replay_window);
+ *   for a kept row with an unknown tag, that violates a size guard (PackError::TooBig), has a child
+ *     range outside n_children, is a container with elements but no child columns, or nests past
+ *     NXG_MAX_DEPTH: the message names the lowest such window row and its cause, whatever the
+ *     scheduling;
+ *   when rec_items[i] * size_of::<BatchItem>() (24) exceeds MAX_VEC (TooBig; the first such record);
+ *   when n_bytes > cap_bytes: n_bytes, n_items, n_dropped, n_kept_recs, rec_off and rec_items then
+ *     hold the true values.
+ * Every check and every size is settled before the first byte of `out` is written: after any false
+ * return no byte of `out` has changed. Whatever the outcome, nothing outside [out, out +
+ * cap_bytes), rec_off[0 .. n_recs] and rec_items[0 .. n_recs) is written. n_recs == 0, or records
+ * without rows, gives all zeros and launches nothing. Synchronous, one copy up of the records' rows
+ * and timestamps, one read-back of a small head; out NULL sizes only. */
+typedef struct NxgOneshotDeltas {
+    uint64_t cap_bytes; uint8_t* out;   /* device; NULL: size only */
+    uint64_t* rec_off;                  /* device [n_recs + 1]: record i's element is out[rec_off[i], rec_off[i+1]) */
+    uint64_t* rec_items;                /* device [n_recs]: items kept in record i */
+    uint64_t n_bytes, n_items, n_dropped, n_kept_recs;   /* written by the call */
+} NxgOneshotDeltas;
+bool nxg_oneshot_pack_deltas(NxgCtx* ctx, const NxgColumns* window, const uint8_t* dbuf,
+                             const NxgArchiveBatchInfo* info /* host [n_recs] */, uint32_t n_recs,
+                             const int64_t* ts_secs, const uint32_t* ts_nanos /* host [n_recs] each */,
+                             const uint8_t* sel /* device [n_ids] */, uint64_t n_ids,
+                             NxgOneshotDeltas* out, NetidxError* err);
+
+/* The framing of a shard and of the reply: host arithmetic, no ctx.
+ * nxg_oneshot_shard_layout: from the lengths of the shard's pathmap and image sections, the summed
+ * bytes of its deltas fragments (deltas_len) and the number of delta records in them (n_deltas),
+ * the two small heads and where everything lies. With inner = pathmap_len + image_len +
+ * varint_len(n_deltas) + deltas_len, Ls = len_wrapped_len(inner) = inner + varint_len(inner +
+ * varint_len(inner)); the shard is len_head | pathmap | image | count_head | fragments.
+ * nxg_oneshot_reply_head: from the shards' lengths, head = varint(Lr) varint(n_shards) (at most 20
+ * bytes) with Lr = len_wrapped_len(varint_len(n_shards) + the shards' bytes); *reply_len (may be
+ * NULL) = the head and the shards. The reply is head | shard | shard ... .
+ * VecDeque::encode and Vec::encode guard count * size_of::<T>() against MAX_VEC (pack.rs:1066,
+ * 943); the element sizes involve GPooled<..> and are not pinned by the reference tree, so both
+ * calls refuse a count above MAX_VEC / 64 (n_deltas; n_shards). Besides that: a null argument, a
+ * section of 2^60 bytes or more, shards that sum to 2^60 bytes or more. */
+typedef struct NxgOneshotShardLayout {
+    uint64_t pathmap_len, image_len, deltas_len, n_deltas;   /* as given */
+    uint64_t pathmap_off, image_off, count_off, deltas_off;  /* where each part starts in the shard */
+    uint64_t shard_len;                                      /* all of the shard, len_head included */
+    uint32_t len_head_len, count_head_len;
+    uint8_t len_head[10];                                    /* varint(Ls), at offset 0 */
+    uint8_t count_head[10];                                  /* varint(n_deltas), at count_off */
+    uint8_t pad[4];
+} NxgOneshotShardLayout;
+bool nxg_oneshot_shard_layout(uint64_t pathmap_len, uint64_t image_len, uint64_t deltas_len,
+                              uint64_t n_deltas, NxgOneshotShardLayout* out, NetidxError* err);
+bool nxg_oneshot_reply_head(const uint64_t* shard_len, uint64_t n_shards, uint8_t* head /* [20] */,
+                            uint32_t* head_len, uint64_t* reply_len, NetidxError* err);
+/* A shard put together in device memory: `layout` as nxg_oneshot_shard_layout made it, pathmap and
+ * image the sections (device, layout->pathmap_len and ->image_len bytes), frags the deltas
+ * fragments in order (device; a fragment of length 0 is skipped). Device-to-device copies to the
+ * layout's offsets on the ctx's stream, the two heads from pinned staging; *len_out (may be NULL) =
+ * layout->shard_len. Synchronous. false, before anything is copied: a null argument by name, a
+ * layout that is not nxg_oneshot_shard_layout's, fragments whose lengths do not sum to
+ * layout->deltas_len, cap < layout->shard_len, host memory, async work pending on the ctx. Nothing
+ * outside [out, out + cap) is written. */
+typedef struct NxgOneshotFrag {
+    const uint8_t* ptr;   /* device */
+    uint64_t len;
+} NxgOneshotFrag;
+bool nxg_oneshot_assemble_shard(NxgCtx* ctx, const NxgOneshotShardLayout* layout,
+                                const uint8_t* pathmap, const uint8_t* image,
+                                const NxgOneshotFrag* frags, uint32_t n_frags, uint8_t* out,
+                                uint64_t cap, uint64_t* len_out, NetidxError* err);
+
 /* ---- the publisher <-> subscriber connection (BASELINE configs[0]) ------------------------
  * Replaces hello_publisher (netidx/src/subscriber/connection.rs:120-140), ClientCtx::hello
  * (publisher/server.rs:367-381), read_task / flush_buf (channel.rs:107-126, 379-443) and the

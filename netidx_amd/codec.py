@@ -130,6 +130,35 @@ class NxgArchiveIndexes(C.Structure):
 INDEX_NONE, INDEX_MATCH, INDEX_ERR_SHORT, INDEX_ERR_FORMAT = 0, 1, 2, 3
 
 
+class NxgOneshotPaths(C.Structure):
+    _fields_ = [("n_ids", C.c_uint64), ("path_off", C.c_void_p), ("path_bytes", C.c_void_p)]
+
+
+class NxgOneshotPathmap(C.Structure):
+    _fields_ = [("cap_bytes", C.c_uint64), ("out", C.c_void_p), ("sel", C.c_void_p),
+                ("n_bytes", C.c_uint64), ("n_sel", C.c_uint64)]
+
+
+class NxgOneshotDeltas(C.Structure):
+    _fields_ = [("cap_bytes", C.c_uint64), ("out", C.c_void_p), ("rec_off", C.c_void_p),
+                ("rec_items", C.c_void_p), ("n_bytes", C.c_uint64), ("n_items", C.c_uint64),
+                ("n_dropped", C.c_uint64), ("n_kept_recs", C.c_uint64)]
+
+
+class NxgOneshotShardLayout(C.Structure):
+    _fields_ = [("pathmap_len", C.c_uint64), ("image_len", C.c_uint64),
+                ("deltas_len", C.c_uint64), ("n_deltas", C.c_uint64),
+                ("pathmap_off", C.c_uint64), ("image_off", C.c_uint64),
+                ("count_off", C.c_uint64), ("deltas_off", C.c_uint64), ("shard_len", C.c_uint64),
+                ("len_head_len", C.c_uint32), ("count_head_len", C.c_uint32),
+                ("len_head", C.c_uint8 * 10), ("count_head", C.c_uint8 * 10),
+                ("pad", C.c_uint8 * 4)]
+
+
+class NxgOneshotFrag(C.Structure):
+    _fields_ = [("ptr", C.c_void_p), ("len", C.c_uint64)]
+
+
 class NxgWriteTable(C.Structure):
     _fields_ = [("n_ids", C.c_uint64), ("perm_of_id", C.c_void_p), ("slot_of_id", C.c_void_p),
                 ("n_slots", C.c_uint64), ("slot_chan_off", C.c_void_p), ("chan", C.c_void_p),
@@ -402,6 +431,23 @@ SIGNATURES = {
                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64,
                                           C.c_void_p, C.POINTER(C.c_uint64),
                                           C.POINTER(NetidxError)]),
+    "nxg_oneshot_pack_pathmap": (C.c_bool, [C.c_void_p, C.POINTER(NxgOneshotPaths), C.c_void_p,
+                                            C.POINTER(NxgOneshotPathmap),
+                                            C.POINTER(NetidxError)]),
+    "nxg_oneshot_pack_deltas": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
+                                           C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.POINTER(NxgOneshotDeltas),
+                                           C.POINTER(NetidxError)]),
+    "nxg_oneshot_shard_layout": (C.c_bool, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.POINTER(NxgOneshotShardLayout),
+                                            C.POINTER(NetidxError)]),
+    "nxg_oneshot_reply_head": (C.c_bool, [C.c_void_p, C.c_uint64, C.c_void_p,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                          C.POINTER(NetidxError)]),
+    "nxg_oneshot_assemble_shard": (C.c_bool, [C.c_void_p, C.POINTER(NxgOneshotShardLayout),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                              C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                              C.POINTER(NetidxError)]),
     "nxg_encode_clients": (C.c_bool, [C.c_void_p, C.POINTER(NxgColumns), C.c_void_p,
                                       C.POINTER(NxgDispatch), C.c_uint32,
                                       C.POINTER(NxgClientFrames), C.POINTER(NetidxError)]),
@@ -1342,6 +1388,150 @@ class Codec:
             keep.data_ptr() if n_ids else None, n_ids, verdict.ctypes.data, C.byref(nm),
             C.byref(err)), err)
         return verdict[:n], nm.value
+
+    def oneshot_pack_pathmap_into(self, path_off, path_bytes, keep, out_ptr, cap, sel=None):
+        """nxg_oneshot_pack_pathmap into device memory at `out_ptr` (0 / None: size only).
+        path_off: int64 device tensor of n_ids + 1 offsets into path_bytes (uint8 device tensor),
+        keep: uint8 device tensor of n_ids flags (filter.is_match per Id). Returns (n_bytes, sel,
+        n_sel): sel the uint8 device tensor the call wrote, the `keep` of scan_index, the image
+        and oneshot_pack_deltas. A CodecError raised here carries n_bytes, n_sel and sel."""
+        import torch
+        n_ids = max(path_off.numel() - 1, 0)
+        if sel is None:
+            sel = torch.empty(max(n_ids, 1), dtype=torch.uint8, device=path_off.device)
+        p = NxgOneshotPaths(n_ids, path_off.data_ptr() if n_ids else None,
+                            path_bytes.data_ptr() if path_bytes is not None and
+                            path_bytes.numel() else None)
+        o = NxgOneshotPathmap(cap, out_ptr or None, sel.data_ptr(), 0, 0)
+        err = NetidxError()
+        try:
+            _check(lib().nxg_oneshot_pack_pathmap(self.ctx, C.byref(p),
+                                                  keep.data_ptr() if n_ids else None,
+                                                  C.byref(o), C.byref(err)), err)
+        except CodecError as e:
+            e.n_bytes, e.n_sel, e.sel = int(o.n_bytes), int(o.n_sel), sel
+            raise
+        return int(o.n_bytes), sel[:n_ids], int(o.n_sel)
+
+    def oneshot_pack_pathmap(self, path_off, path_bytes, keep, out=None):
+        """The filter set and the pathmap section of a oneshot reply shard (oneshot.rs:111-120) in
+        one call. Returns (bytes, sel, n_sel): bytes = varint(n_sel) and, per selected Id in
+        ascending order, varint(id) varint(len) path (a uint8 tensor on path_off's device). `out`:
+        a uint8 device tensor to write into (all of it is the capacity); without one the call
+        sizes first and allocates."""
+        import torch
+        sel = None
+        if out is None:
+            n, sel, _ = self.oneshot_pack_pathmap_into(path_off, path_bytes, keep, None, 0)
+            out = torch.empty(max(n, 16), dtype=torch.uint8, device=path_off.device)
+            cap = n
+        else:
+            cap = out.numel()
+        n, sel, n_sel = self.oneshot_pack_pathmap_into(path_off, path_bytes, keep,
+                                                       out.data_ptr(), cap, sel)
+        return out[:n], sel, n_sel
+
+    def oneshot_pack_deltas_into(self, cols, infos, ts_secs, ts_nanos, sel, heap, out_ptr, cap,
+                                 rec_off=None, rec_items=None):
+        """nxg_oneshot_pack_deltas into device memory at `out_ptr` (0 / None: size only). cols /
+        infos: archive_decode_window's columns and per-record infos (or (row_off, n_rows) pairs);
+        ts_secs / ts_nanos: the records' timestamps (host sequences); sel: oneshot_pack_pathmap's
+        uint8 device tensor (or None: no Id is kept); heap: the buffer the window was decoded
+        from. Returns (n_bytes, rec_off, rec_items, n_items, n_dropped, n_kept_recs); a CodecError
+        raised here carries n_bytes, rec_off and rec_items."""
+        import torch
+        n = len(infos)
+        info = (NxgArchiveBatchInfo * max(n, 1))()
+        for i, t in enumerate(infos):
+            if isinstance(t, NxgArchiveBatchInfo):
+                info[i].row_off, info[i].n_rows = t.row_off, t.n_rows
+            else:
+                info[i].row_off, info[i].n_rows = t[0], t[1]
+        secs = np.ascontiguousarray(ts_secs, dtype=np.int64)
+        nanos = np.ascontiguousarray(ts_nanos, dtype=np.uint32)
+        assert len(secs) == n and len(nanos) == n
+        dev = cols.id.device
+        if rec_off is None:
+            rec_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        if rec_items is None:
+            rec_items = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        n_ids = sel.numel() if sel is not None else 0
+        o = NxgOneshotDeltas(cap, out_ptr or None, rec_off.data_ptr(), rec_items.data_ptr(),
+                             0, 0, 0, 0)
+        err = NetidxError()
+        try:
+            _check(lib().nxg_oneshot_pack_deltas(
+                self.ctx, C.byref(cols.s), _heap_ptr(heap), info if n else None, n,
+                secs.ctypes.data if n else None, nanos.ctypes.data if n else None,
+                sel.data_ptr() if n_ids else None, n_ids, C.byref(o), C.byref(err)), err)
+        except CodecError as e:
+            e.n_bytes, e.rec_off, e.rec_items = int(o.n_bytes), rec_off, rec_items
+            raise
+        return (int(o.n_bytes), rec_off, rec_items[:n], int(o.n_items), int(o.n_dropped),
+                int(o.n_kept_recs))
+
+    def oneshot_pack_deltas(self, cols, infos, ts_secs, ts_nanos, sel, heap=None, out=None):
+        """batch.retain, the empty-record drop and the deltas elements of one window in one call
+        (oneshot.rs:146-149). Returns (bytes, rec_off, rec_items, n_dropped, n_kept_recs): record
+        i's element  secs nanos varint(items) item...  is bytes[rec_off[i]:rec_off[i+1]] (empty
+        when it keeps nothing); the fragments of successive windows concatenate into the deltas
+        section behind its count. `out`: a uint8 device tensor to write into (all of it is the
+        capacity); without one the call sizes first and allocates."""
+        import torch
+        off = items = None
+        if out is None:
+            n, off, items, _, _, _ = self.oneshot_pack_deltas_into(cols, infos, ts_secs, ts_nanos,
+                                                                   sel, heap, None, 0)
+            out = torch.empty(max(n, 16), dtype=torch.uint8, device=cols.id.device)
+            cap = n
+        else:
+            cap = out.numel()
+        n, off, items, _, dropped, kept = self.oneshot_pack_deltas_into(
+            cols, infos, ts_secs, ts_nanos, sel, heap, out.data_ptr(), cap, off, items)
+        return out[:n], off, items, dropped, kept
+
+    @staticmethod
+    def oneshot_shard_layout(pathmap_len, image_len, deltas_len, n_deltas):
+        """nxg_oneshot_shard_layout (host arithmetic, no context): the NxgOneshotShardLayout of a
+        shard whose sections have these lengths and whose deltas fragments hold n_deltas
+        records."""
+        lay, err = NxgOneshotShardLayout(), NetidxError()
+        _check(lib().nxg_oneshot_shard_layout(pathmap_len, image_len, deltas_len, n_deltas,
+                                              C.byref(lay), C.byref(err)), err)
+        return lay
+
+    @staticmethod
+    def oneshot_reply_head(shard_lens):
+        """nxg_oneshot_reply_head (host arithmetic, no context): (head, reply_len), head =
+        varint(Lr) varint(n_shards) as bytes; the reply is head + the shards."""
+        lens = np.ascontiguousarray(shard_lens, dtype=np.uint64)
+        head = (C.c_uint8 * 20)()
+        hl, rl, err = C.c_uint32(0), C.c_uint64(0), NetidxError()
+        _check(lib().nxg_oneshot_reply_head(lens.ctypes.data if len(lens) else None, len(lens),
+                                            head, C.byref(hl), C.byref(rl), C.byref(err)), err)
+        return bytes(head[:hl.value]), rl.value
+
+    def oneshot_assemble_shard(self, layout, pathmap, image, frags, out=None):
+        """nxg_oneshot_assemble_shard: the shard len_head | pathmap | image | count_head |
+        fragments in device memory. pathmap / image / frags: uint8 device tensors (frags a
+        sequence, possibly empty). Returns the shard's bytes, a uint8 device tensor (`out`, or a
+        new one of layout.shard_len bytes)."""
+        import torch
+        if out is None:
+            out = torch.empty(max(int(layout.shard_len), 16), dtype=torch.uint8,
+                              device=pathmap.device)
+            cap = int(layout.shard_len)
+        else:
+            cap = out.numel()
+        fr = (NxgOneshotFrag * max(len(frags), 1))()
+        for i, f in enumerate(frags):
+            fr[i] = NxgOneshotFrag(f.data_ptr() if f.numel() else None, f.numel())
+        n, err = C.c_uint64(0), NetidxError()
+        _check(lib().nxg_oneshot_assemble_shard(
+            self.ctx, C.byref(layout), pathmap.data_ptr() if pathmap.numel() else None,
+            image.data_ptr() if image.numel() else None, fr if len(frags) else None, len(frags),
+            out.data_ptr(), cap, C.byref(n), C.byref(err)), err)
+        return out[:n.value]
 
     def encoded_len(self, cols, heap=None):
         n, err = C.c_uint64(0), NetidxError()

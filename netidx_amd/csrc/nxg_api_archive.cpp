@@ -10,6 +10,45 @@
 
 using namespace nxg_host;
 
+// ---- what other archive-side files share (nxg_host.h) ------------------------------------------
+const char* nxg_host::rec_cause(uint32_t cause) {
+    switch (cause) {
+    case kRecRow: return "ent_row names a row at or past the batch's n_rows";
+    case kRecTag: return "an unknown tag (PackError kind 1)";
+    case kRecBig: return "a size guard (PackError::TooBig)";
+    case kRecKids: return "a child range outside the batch's n_children";
+    case kRecNoKids: return "a container with elements but no child columns";
+    case kRecDepth: return "a value nested deeper than NXG_MAX_DEPTH";
+    default: return "unknown cause";
+    }
+}
+
+bool nxg_host::window_records(const NxgColumns* window, const NxgArchiveBatchInfo* info,
+                              uint32_t n_recs, std::vector<uint64_t>* hbeg,
+                              std::vector<uint64_t>* hend, NetidxError* err) {
+    hbeg->assign((size_t)n_recs + 1, 0);
+    hend->assign(n_recs, 0);
+    for (uint32_t i = 0; i < n_recs; i++) {
+        const uint64_t lo = info[i].row_off, cnt = info[i].n_rows;
+        if (lo > window->n_rows || cnt > window->n_rows - lo) {
+            set_err(err, "info[%u]: rows [%llu, + %llu) leave the window's %llu rows", i,
+                    (unsigned long long)lo, (unsigned long long)cnt,
+                    (unsigned long long)window->n_rows);
+            return false;
+        }
+        if (i && lo < (*hend)[i - 1]) {
+            set_err(err, "info[%u].row_off (%llu) lies in front of the end of record %u (%llu): "
+                         "row_off must not decrease and records must not overlap", i,
+                    (unsigned long long)lo, i - 1, (unsigned long long)(*hend)[i - 1]);
+            return false;
+        }
+        (*hbeg)[i] = lo;
+        (*hend)[i] = lo + cnt;
+    }
+    (*hbeg)[n_recs] = n_recs ? (*hend)[n_recs - 1] : 0;
+    return true;
+}
+
 extern "C" {
 
 // ---- archive batches (netidx-archive logfile/mod.rs:150-205) ---------------------------------
@@ -737,20 +776,6 @@ bool nxg_archive_build_image(NxgCtx* c, const NxgColumns* window, uint64_t n_ids
 
 // ---- a dispatch's entries as archive batch records (the recorder's batch loop, record.rs:307-347)
 // (nxg_record.hip). Argument checks on the host, the launches, one read-back of the call's head.
-namespace {
-const char* rec_cause(uint32_t cause) {
-    switch (cause) {
-    case kRecRow: return "ent_row names a row at or past the batch's n_rows";
-    case kRecTag: return "an unknown tag (PackError kind 1)";
-    case kRecBig: return "a size guard (PackError::TooBig)";
-    case kRecKids: return "a child range outside the batch's n_children";
-    case kRecNoKids: return "a container with elements but no child columns";
-    case kRecDepth: return "a value nested deeper than NXG_MAX_DEPTH";
-    default: return "unknown cause";
-    }
-}
-}  // namespace
-
 bool nxg_record_entries(NxgCtx* c, const NxgColumns* batch, const uint8_t* heap,
                         const NxgDispatch* d, uint32_t n_chans, const NxgRecordTable* tab,
                         NxgRecordBatches* out, NetidxError* err) {
@@ -1045,26 +1070,9 @@ bool nxg_replay_window(NxgCtx* c, const NxgColumns* window, const NxgArchiveBatc
     if (window->mem != NXG_MEM_DEVICE || window->layout != NXG_LAYOUT_MIXED ||
         (window->n_rows && (!window->id || !window->tag || !window->fixed || !window->aux)))
         return refuse(err, "a window is replayed from device MIXED-layout columns");
-    std::vector<uint64_t> hbeg((size_t)n_recs + 1), hend(n_recs);
-    for (uint32_t i = 0; i < n_recs; i++) {
-        const uint64_t lo = info[i].row_off, cnt = info[i].n_rows;
-        if (lo > window->n_rows || cnt > window->n_rows - lo) {
-            set_err(err, "info[%u]: rows [%llu, + %llu) leave the window's %llu rows", i,
-                    (unsigned long long)lo, (unsigned long long)cnt,
-                    (unsigned long long)window->n_rows);
-            return false;
-        }
-        if (i && lo < hend[i - 1]) {
-            set_err(err, "info[%u].row_off (%llu) lies in front of the end of record %u (%llu): "
-                         "row_off must not decrease and records must not overlap", i,
-                    (unsigned long long)lo, i - 1, (unsigned long long)hend[i - 1]);
-            return false;
-        }
-        hbeg[i] = lo;
-        hend[i] = lo + cnt;
-    }
-    const uint64_t first = n_recs ? hbeg[0] : 0, n = n_recs ? hend[n_recs - 1] - first : 0;
-    hbeg[n_recs] = first + n;
+    std::vector<uint64_t> hbeg, hend;
+    if (!window_records(window, info, n_recs, &hbeg, &hend, err)) return false;
+    const uint64_t first = hbeg[0], n = hbeg[n_recs] - first;
     if (!no_pending(c, err)) return false;
     if (!set_device(c, err)) return false;
     if (!replay_out_ok(out, "nxg_replay_window", err)) return false;

@@ -6,6 +6,8 @@
 //   nxg_api.cpp          update decode / encode, the async backlog, nxg_ctx_sync, To batches
 //   nxg_api_archive.cpp  archive batches, zstd, windows and images, recording, the RecordIndex,
 //                        replay
+//   nxg_api_oneshot.cpp  a oneshot reply: the pathmap and deltas sections, the shard's and the
+//                        reply's framing
 //   nxg_api_fanout.cpp   partition, dispatch, publish, per-client frames, the value table
 //   nxg_api_route.cpp    write / Subscribe / reply routing, the path table
 //   nxg_api_range.cpp    byte-range and share decode (multi-GPU)
@@ -170,6 +172,8 @@ struct NxgCtx {
     DevBuf<uint8_t> aix_table;
     DevBuf<uint8_t> aix_dev;
     DevBuf<uint8_t, DevMem::Pinned> aix_host;
+    // nxg_oneshot_assemble_shard: pinned staging of the shard's two small heads
+    DevBuf<uint8_t, DevMem::Pinned> os_host;
     uint64_t last_split = 0;  // last completed encode's DevStatus.split_start
 };
 
@@ -284,6 +288,15 @@ bool copy_cols_d2h(NxgCtx* c, const NxgColumns* d, NxgColumns* h, NetidxError* e
 bool copy_cols_h2d(NxgCtx* c, const NxgColumns* h, NxgColumns* d, NetidxError* err);
 bool frame_to_device(NxgCtx* c, const uint8_t* frame, uint64_t len, const uint8_t** df,
                      NetidxError* err);
+
+// ---- archive calls (nxg_api_archive.cpp) -------------------------------------------------------
+// The records of a decoded window as row ranges: hbeg[i] / hend[i] for record i and hbeg[n_recs] =
+// the end of the last record (0 without records). false: an info whose rows leave the window,
+// whose row_off decreases or whose rows overlap the record before (the message says which).
+bool window_records(const NxgColumns* window, const NxgArchiveBatchInfo* info, uint32_t n_recs,
+                    std::vector<uint64_t>* hbeg, std::vector<uint64_t>* hend, NetidxError* err);
+// the words for a kRec* cause (nxg_record.h) of a refused entry or window row
+const char* rec_cause(uint32_t cause);
 
 // ---- update decode / encode (nxg_api.cpp) ------------------------------------------------------
 // path codes of a fast attempt (Pending::fast): homogeneous f64 (SEQ, RUN, X) or mixed (MIX)
